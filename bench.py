@@ -28,6 +28,12 @@ value = fitted spots/s over all ranks; `fovs_per_sec` beside it.  Extra objects 
                 configs[4] (uint16 4-colour movie -> corrections -> drift -> warp -> fit)
   cpu_baseline  the NumPy/SciPy oracle (restatement of the reference's CPU path, pinned against it) on the WHOLE first FOV,
                 one core; beside it one window per core on all of this box's cores (N=1 only)
+streaming, secondary and cpu_baseline run only with `--full`: a plain run sets up, warms up, times the steps and prints the
+line (the objects above it come from the timed steps' own HIP events and counters).
+
+`--dump-outputs DIR` writes, after the timed steps, the spot tables of the last step (what `ia3_fit_fov_dev` hands its
+caller: one (n, 11) float32 table per FOV) as DIR/spots_fov<j>.npy, rank 0's only.  The inputs are generated from fixed
+seeds, so two builds run with the same arguments can be compared table for table.
 """
 import argparse
 import json
@@ -50,6 +56,7 @@ MAX_SEEDS = 8192               # rows per FOV of the gathered block (the referen
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
 F64_VALU_PEAK_TFLOPS = 78.6    # MI355X FP64 vector peak (FMA = 2 flop)
 FIT_FLOP_PER_VOXEL_EVAL = 254  # ia3_model.h model_jac + residual + J^T J / J^T r accumulation, exp = 20
+DUMP_LIMIT_BYTES = 64 << 20    # --dump-outputs writes at most this much
 
 
 def parse():
@@ -64,7 +71,24 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-secondary", action="store_true", help="skip the streaming / uint16 / configs[2] / configs[4] legs")
     ap.add_argument("--cpu-crop", type=int, default=0, help="x/y edge of the CPU baseline's window; 0 = the whole FOV (about a minute on one core)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also the streaming and secondary legs and the CPU baseline (N=1 only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the spot tables of the last timed step as DIR/spots_fov<j>.npy (float32)")
     return ap.parse_args()
+
+
+def dump_outputs(dirname, tables):
+    """The last timed step's spot tables, one (n, 11) float32 file per FOV in step order.  Should they come to more than
+    DUMP_LIMIT_BYTES (a step of very many FOVs), the first ones in step order are written and the rest left out."""
+    os.makedirs(dirname, exist_ok=True)
+    used = 0
+    for j, t in enumerate(tables):
+        arr = np.ascontiguousarray(t, dtype=np.float32)
+        used += arr.nbytes + 128   # + the .npy header
+        if used > DUMP_LIMIT_BYTES:
+            break
+        np.save(os.path.join(dirname, "spots_fov%d.npy" % j), arr)
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -181,6 +205,8 @@ def main():
     a = parse()
     if a.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if a.steps < 1 or a.warmup < 0:
+        raise SystemExit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and a.gpus > 1:
         return launch_ranks(a)
     rank = int(os.environ.get("RANK", "0"))
@@ -190,7 +216,8 @@ def main():
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     shape = tuple(a.shape)
     full = shape == SHAPE
-    extra = world == 1 and not a.no_secondary
+    extra = world == 1 and a.full and not a.no_secondary
+    with_cpu = world == 1 and a.full and not a.no_cpu_baseline
     ncore = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
     # ---- host-side work first (forks workers: must precede the first GPU call of this process) ---------------------
     t0 = time.time()
@@ -207,7 +234,7 @@ def main():
     fovs = [arrs["f32_%d" % k][0] for k in range(a.pool)]
     gen_s = time.time() - t0
     cpu_base = None
-    if not a.no_cpu_baseline and world == 1:
+    if with_cpu:
         cpu_base = cpu_baseline(fovs[0], a.cpu_crop)
     forked = None
     if extra:   # children that open the GPU themselves: before this process does
@@ -290,9 +317,9 @@ def main():
     step_s = []
     for i in range(a.warmup, a.warmup + a.steps):
         ts = time.perf_counter()
-        t, last = step(i)          # returns with the step's table on the host: no further synchronisation needed to time it
+        last_tables, last = step(i)   # returns with the step's table on the host: no further synchronisation needed to time it
         step_s.append(time.perf_counter() - ts)
-        tables.extend(t)
+        tables.extend(last_tables)
     # final spot-table all-gather: counts + the padded [fovs_per_rank, max_seeds, 11] f32 block of EVERY table of the
     # timed region (the reference's on-disk layout, field_of_view.py:1361-1382) — the path's only exchange
     table = gather_spot_tables(tables, MAX_SEEDS, world)
@@ -300,6 +327,8 @@ def main():
     dt = time.perf_counter() - t0
     prof = L.profile_collect()
     L.profile_enable(False)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last_tables)
     total_rows = sum(len(t) for t in tables)
     if world > 1:
         t = torch.tensor([dt, float(total_rows)], dtype=torch.float64,
@@ -461,7 +490,7 @@ def main():
                     forked["batch_entry_fovs_per_sec"] = u["fovs_per_sec"]
                     forked["frac_of_batch_entry"] = round(forked["fovs_per_sec"] / u["fovs_per_sec"], 3)
                 out["secondary"]["forked_pool"] = forked
-        if not a.no_cpu_baseline:
+        if a.full and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_base   # None for multi-GPU runs (measured at N=1 only)
     for s in stacks:
         s.free()

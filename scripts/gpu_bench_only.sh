@@ -2,7 +2,7 @@
 set -e -o pipefail
 OUT=gpurun_out/${1:-r04r}
 mkdir -p $OUT
-( time python bench.py ) > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
+( time python bench.py --full ) > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
 tail -4 $OUT/bench.err
 python - <<EOF
 import json

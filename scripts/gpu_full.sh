@@ -9,5 +9,5 @@ tail -3 $OUT/pytest.log
 grep -h "rows \|seeds .*overlapping\|equal-height" $OUT/pytest.log || true
 IA3_BENCH_DEVICE=0 IA3_BENCH_BACKEND=gloo python3 bench.py --gpus 2 --steps 5 --warmup 2 --no-secondary --no-cpu-baseline > $OUT/bench_2rank_rehearsal.json 2> $OUT/bench_2rank_rehearsal.err || { tail -30 $OUT/bench_2rank_rehearsal.err; exit 1; }
 cat $OUT/bench_2rank_rehearsal.json | cut -c 1-600
-python bench.py --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
+python bench.py --full --steps 20 --warmup 5 > $OUT/bench.json 2> $OUT/bench.err || { tail -30 $OUT/bench.err; exit 1; }
 cut -c 1-400 $OUT/bench.json
