@@ -625,6 +625,7 @@ int dog_pair_t(const T* src, int Z, int X, int Y, const Taps& ft, const Taps& bt
     else rc = folded_pair_u16(src, Z, plane, bt, dst_zp, ft, tmp, s, cert, smin, sabs, Y);
   }
   if (rc) return rc;   // FOLD_NOT_COVERED, or an error (negative)
+  if (!dst_front) return FOLD_NO_FORK;   // the caller runs axes 1 and 2 of the short filter on tmp itself (seed_front_k)
   // axes 1 and 2 of the short filter: tmp -> dst_front (the caller goes on with dst_zp on the auxiliary stream)
   int TY, ntile;
   ia3k::dog_pair_tiles(X, Y, &TY, &ntile, nullptr);
@@ -835,8 +836,11 @@ int gaussian3d(const void* src, int dtype, int Z, int X, int Y, const double* w,
 // of the long filter (wb, radius rb) -> dst_zp, both 'reflect'.  The two axis-0 passes share one launch and every load;
 // the short filter's other two axes are queued on the auxiliary stream.  Returns 0 with *forked = 1 when the caller
 // has to aux_join() before reading dst_front, 1 when this shape / these radii are not covered (nothing was queued).
+// dst_front == nullptr: the column kernel only (tmp = the short filter's axis-0 result, dst_zp), no fork.
 // geometry of the plane-wise kernel: y tiles of TY columns, steps of 16 rows; *count = entries per plane of the table of
 // step maxima (one per 16 rows x 64 columns = per tile of the candidate detector)
+const int* reflect_map(int count, int R, int len) { return cached_border_map(count, R, len, IA3_MODE_REFLECT); }
+
 void dog_pair_tiles(int X, int Y, int* ty, int* ntile, size_t* count) {
   const int ncol = (Y + 63) / 64;              // 64-column groups = the detector's tile columns
   *ty = 64 * (ncol < 3 ? ncol : 3);            // a y tile holds whole groups: 192 columns (198 of 256 threads on axis 1)
@@ -904,6 +908,7 @@ int ia3_set_tuning(int key, int value) {
   if (key == IA3_TUNE_UPLOAD_THREADS) return ia3rt::set_upload_threads(value);
   if (key == IA3_TUNE_SEED_DENSE) { ia3k::set_seed_dense(value); return 0; }
   if (key == IA3_TUNE_SEED_STRIPS) { ia3k::set_seed_strips(value); return 0; }
+  if (key == IA3_TUNE_SEED_FUSED) { ia3k::set_seed_fused(value); return 0; }
   if (key == IA3_TUNE_FIT_NBLIST) { ia3k::set_fit_nblist(value); return 0; }
   if (key == IA3_TUNE_FFT_C2C) { ia3k::set_fft_c2c(value); return 0; }
   if (key == IA3_TUNE_FIT_FUSE) { ia3k::set_fit_fuse(value); return 0; }

@@ -16,6 +16,7 @@
 // Otherwise, and as the fallback when the lazy form's candidate list overflows: both filtered stacks are read once
 // (8 B/voxel for f32) by an LDS-tiled kernel with a rolling three-plane register pipeline along z.
 #include "ia3_rt.h"
+#include "ia3_gauss_dev.h"
 #include <memory>
 #include <algorithm>
 #include <math.h>
@@ -337,13 +338,9 @@ __global__ __launch_bounds__(256) void blockbound_k(const float* __restrict__ bm
 // the 3 x 3 block neighbourhood, one value per plane group, written for every plane of the group.  Coarser along z than the
 // per-plane block minima (the axis-0 result is smooth along z by construction); the extra uint16 count covers outputs the
 // column kernel recomputes after taking their minimum (they may differ from the stored value by one count / one ulp).
-__global__ __launch_bounds__(256) void stripbound_k(const float* __restrict__ smin, const float* __restrict__ sabs, int Z, int X,
-                                                    int nbx, int nby, int ngz, int is_u16, double* __restrict__ lb) {
-  // one wave per (plane group, block): its lanes share the <= 96 rows x 3 strips of the neighbourhood
-  const size_t i = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (i >= (size_t)ngz * nbx * nby) return;   // whole wave
-  const int lane = threadIdx.x & 63;
-  const int by = (int)(i % nby), bx = (int)((i / nby) % nbx), g = (int)(i / ((size_t)nbx * nby));
+// One whole wave per call: its lanes share the <= 96 rows x 3 strips of block (bx, by)'s neighbourhood in plane group g.
+__device__ __forceinline__ double strip_bound(const float* __restrict__ smin, const float* __restrict__ sabs, int X, int nby,
+                                              int g, int bx, int by, int is_u16, int lane) {
   const int x0 = max(32 * (bx - 1), 0), x1 = min(32 * (bx + 2), X), y0 = max(by - 1, 0), ny = min(by + 1, nby - 1) - y0 + 1;
   float m = INFINITY, a = 0.f;
   for (int e = lane; e < (x1 - x0) * ny; e += 64) {
@@ -352,7 +349,17 @@ __global__ __launch_bounds__(256) void stripbound_k(const float* __restrict__ sm
   }
 #pragma unroll
   for (int o = 32; o >= 1; o >>= 1) { m = fminf(m, __shfl_xor(m, o)); a = fmaxf(a, __shfl_xor(a, o)); }
-  const double v = (double)m - 2e-6 * (double)a - (is_u16 ? 3.0 : 0.0);
+  return (double)m - 2e-6 * (double)a - (is_u16 ? 3.0 : 0.0);
+}
+
+__global__ __launch_bounds__(256) void stripbound_k(const float* __restrict__ smin, const float* __restrict__ sabs, int Z, int X,
+                                                    int nbx, int nby, int ngz, int is_u16, double* __restrict__ lb) {
+  // one wave per (plane group, block)
+  const size_t i = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= (size_t)ngz * nbx * nby) return;   // whole wave
+  const int lane = threadIdx.x & 63;
+  const int by = (int)(i % nby), bx = (int)((i / nby) % nbx), g = (int)(i / ((size_t)nbx * nby));
+  const double v = strip_bound(smin, sabs, X, nby, g, bx, by, is_u16, lane);
   for (int z = lane; z < Z; z += 64)
     if (z * ngz / Z == g) lb[((size_t)z * nbx + bx) * nby + by] = v;
 }
@@ -472,6 +479,181 @@ __global__ __launch_bounds__(256) void seed_cand3_tiled(const T* __restrict__ mx
           else ctl->overflow = 1;
         }
       }
+    }
+  }
+}
+
+// ---- front filter and candidate test in one pass (the lazy paired path) -------------------------------------------
+// max_im is read by nothing but the candidate test, so it need not exist as a stack: a 256-thread block owns a tile of
+// FT_X rows x FT_Y columns and walks a chunk of planes along z.  Per plane (the chunk's planes and one halo plane on
+// either side, index clamped as the detector's 3-window clamps it):
+//   axis 1: A = axis-1 pass of `in` (the short filter's axis-0 result, which the column kernel wrote) at rows x0-1 ..
+//           x0+FT_X and columns y0-4 .. y0+FT_Y+3 (reflected), in registers from a column window, quantised, into LDS;
+//   axis 2: M = max_im at rows x0-1 .. x0+FT_X, columns y0-1 .. y0+FT_Y, runs of four from 16-byte LDS pieces;
+//   test:   3x3 maximum of M at clamped neighbours (= the rank filter's reflect), a rolling three-plane maximum in
+//           registers, and seed_cand3_tiled's test against the lower bound of min_im.
+// Both passes are gauss_xy_short's sequence (acc = v[0]*w0; acc = acc + (v[-j] + v[+j]) * w[j], j = 3..1, unfused,
+// cvt<T> after each axis), so every max_im value, and with it the Cand0 list, is the two-kernel path's bit for bit.
+// The input rows of the next plane are fetched as soon as the current plane's are in registers.
+// Bound: with strip minima (smin != nullptr) the block takes its <= 4 blocks' bounds for the chunk's plane groups from
+// them in a prologue (stripbound_k's reduction, one wave per 32-column block), otherwise it reads lb.
+constexpr int FT_X = 16, FT_Y = 128;
+constexpr int FT_AR = FT_X + 2, FT_AC = FT_Y + 8, FT_MC = FT_Y + 2, FT_MP = FT_Y + 4;   // A rows / columns, M columns / pitch
+constexpr int FT_R1 = FT_AR / 2;                 // axis-1 outputs per thread (two threads per column of A)
+constexpr int FT_NIN = FT_R1 + 6;                // their input rows
+constexpr int FT_VX = FT_X / 2;                  // voxels per thread in the test (two threads per column of the tile)
+struct Taps3 { double w[4]; };
+
+template <class T>
+__global__ __launch_bounds__(256, 4) void seed_front_k(const T* __restrict__ in, const int* __restrict__ mxr, const int* __restrict__ myr,
+                                                    Taps3 taps, int Z, int X, int Y, int zc, int edge, double th_test,
+                                                    const double* __restrict__ lb, const float* __restrict__ smin,
+                                                    const float* __restrict__ sabs, int ngz, Cand0* __restrict__ out,
+                                                    unsigned capacity, SeedCtl* __restrict__ ctl) {
+  static_assert(FT_Y == 128 && FT_X % 16 == 0 && 32 % FT_X == 0, "thread mapping below; a tile lies in one row of 32 x 32 bound blocks");
+  __shared__ __attribute__((aligned(16))) float A[FT_AR][FT_AC];   // axis-1 result (a T value held in a float)
+  __shared__ __attribute__((aligned(16))) float M[FT_AR][FT_MP];   // max_im
+  __shared__ double lbs[ia3k::DOG_PAIR_ZGROUPS][FT_Y / 32];
+  const int t = threadIdx.x;
+  const int nty = (Y + FT_Y - 1) / FT_Y, ntx = (X + FT_X - 1) / FT_X;
+  const int tile = xcd_tile(blockIdx.x, nty * ntx);
+  if (tile < 0) return;   // whole block
+  const int x0 = (tile / nty) * FT_X, y0 = (tile % nty) * FT_Y;
+  const int z0 = blockIdx.z * zc, z1 = min(z0 + zc, Z);
+  const int nby = (Y + 31) / 32, nbx = (X + 31) / 32, bx = x0 / 32, by0 = y0 / 32;
+  const int is_u16 = sizeof(T) == 2;
+  if (smin) {
+    const int w = t >> 6, lane = t & 63;
+    if (by0 + w < nby)   // whole wave
+      for (int g = z0 * ngz / Z; g <= (z1 - 1) * ngz / Z; ++g) {
+        const double v = strip_bound(smin, sabs, X, nby, g, bx, by0 + w, is_u16, lane);
+        if (lane == 0) lbs[g][w] = v;
+      }
+  }
+  // addressing: buffer descriptors (the host checks that the stack is below 2^31 bytes); a thread's column offset is
+  // fixed, the row offsets of the main pass are wave-uniform (scalar)
+  const unsigned ES = (unsigned)sizeof(T), rowb = (unsigned)Y * ES, planeb = (unsigned)X * rowb;
+  const __amdgpu_buffer_rsrc_t rin = __builtin_amdgcn_make_buffer_rsrc((void*)in, (short)0, (int)((unsigned)Z * planeb), 0x00020000);
+  // axis 1, main: column k of A, rows h*FT_R1 .. +FT_R1-1; input rows x0-4+h*FT_R1 .. (map mxr[i] = reflect(i - 4))
+  const int k = t & 127, h = __builtin_amdgcn_readfirstlane(t >> 7);
+  const unsigned colb = (unsigned)myr[y0 + k] * ES;
+  unsigned roff[FT_NIN];   // byte offsets of the input rows inside a plane
+#pragma unroll
+  for (int i = 0; i < FT_NIN; ++i) roff[i] = (unsigned)mxr[x0 + h * FT_R1 + i] * rowb;
+  // axis 1, the last 8 columns of A: thread t < 8 * FT_R1 -> column FT_Y + t / FT_R1, rows 2 * (t % FT_R1) and the next
+  const bool ex = t < 8 * FT_R1;
+  const int ke = FT_Y + (ex ? t / FT_R1 : 0), re = ex ? 2 * (t % FT_R1) : 0;
+  const unsigned colbe = (unsigned)myr[y0 + ke] * ES;
+  unsigned roffe[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) roffe[i] = (unsigned)mxr[x0 + re + i] * rowb;
+  const double w0 = taps.w[0], w1 = taps.w[1], w2 = taps.w[2], w3 = taps.w[3];
+  auto a1 = [&](const double* v) -> float {   // centre v[3]
+    double acc = v[3] * w0;
+    acc = acc + (v[0] + v[6]) * w3;
+    acc = acc + (v[1] + v[5]) * w2;
+    acc = acc + (v[2] + v[4]) * w1;
+    return (float)ia3g::cvt<T>(acc);
+  };
+  auto a2 = [&](const float* f) -> float {   // centre f[3]
+    double acc = (double)f[3] * w0;
+    acc = acc + ((double)f[0] + (double)f[6]) * w3;
+    acc = acc + ((double)f[1] + (double)f[5]) * w2;
+    acc = acc + ((double)f[2] + (double)f[4]) * w1;
+    return (float)ia3g::cvt<T>(acc);
+  };
+  T nxt[FT_NIN], nxe[8] = {};
+  auto fetch = [&](int q) {
+    const unsigned pzb = (unsigned)min(max(q, 0), Z - 1) * planeb;
+#pragma unroll
+    for (int i = 0; i < FT_NIN; ++i) nxt[i] = ia3g::buf_ld<T>(rin, colb, pzb + roff[i]);
+    if (ex) {
+#pragma unroll
+      for (int i = 0; i < 8; ++i) nxe[i] = ia3g::buf_ld<T>(rin, colbe + roffe[i], pzb);
+    }
+  };
+  // test: this thread's voxels are rows x0 + FT_VX * hh + v (v < FT_VX) of column y0 + ty
+  const int ty = t & 127, hh = h;
+  const int y = y0 + ty;
+  const int cl = max(y - 1, 0) - (y0 - 1), cc = ty + 1, cr = min(y + 1, Y - 1) - (y0 - 1);   // clamped neighbour columns of M
+  const int jb = min(y, Y - 1) / 32 - by0;
+  const bool rfix0 = x0 == 0, rfix1 = X - x0 + 1 < FT_AR;   // M rows at positions -1 / X inside the tile
+  float m2[FT_VX], pp[FT_VX], cp[FT_VX];   // max of the 3x3 maxima of planes q-2 and q-1, the 3x3 maximum of q-1, the centre of q-1
+  fetch(z0 - 1);
+  __syncthreads();   // lbs
+  for (int q = z0 - 1; q <= z1; ++q) {
+    {
+      double v[FT_NIN], ve[8];
+#pragma unroll
+      for (int i = 0; i < FT_NIN; ++i) v[i] = (double)nxt[i];
+#pragma unroll
+      for (int i = 0; i < 8; ++i) ve[i] = (double)nxe[i];
+      if (q < z1) fetch(q + 1);   // in flight under the whole of this plane
+#pragma unroll
+      for (int o = 0; o < FT_R1; ++o) A[h * FT_R1 + o][k] = a1(v + o);
+      if (ex) {
+        A[re][ke] = a1(ve);
+        A[re + 1][ke] = a1(ve + 1);
+      }
+    }
+    __syncthreads();   // A complete; every read of the previous plane's M is behind this barrier
+    // axis 2: runs of four outputs (M columns 4u .. 4u+3 from A columns 4u .. 4u+9), then M columns 128 and 129
+    for (int it = t; it < FT_AR * 32 + FT_AR * 2; it += 256) {
+      if (it < FT_AR * 32) {
+        const int r = it >> 5, u = (it & 31) * 4;
+        float f[12];
+#pragma unroll
+        for (int j = 0; j < 3; ++j) *reinterpret_cast<float4*>(&f[4 * j]) = *reinterpret_cast<const float4*>(&A[r][u + 4 * j]);
+        float4 res;
+        res.x = a2(f); res.y = a2(f + 1); res.z = a2(f + 2); res.w = a2(f + 3);
+        *reinterpret_cast<float4*>(&M[r][u]) = res;
+      } else {
+        const int e = it - FT_AR * 32, r = e >> 1, c = FT_Y + (e & 1);
+        float f[7];
+#pragma unroll
+        for (int j = 0; j < 7; ++j) f[j] = A[r][c + j];
+        M[r][c] = a2(f);
+      }
+    }
+    __syncthreads();   // M complete
+    if (rfix0 | rfix1) {   // (uniform) clamp the rows outside the image: row -1 holds row 0, row X holds row X - 1
+      if (t < FT_MC) {
+        if (rfix0) M[0][t] = M[1][t];
+        if (rfix1) M[X - x0 + 1][t] = M[X - x0][t];
+      }
+      __syncthreads();
+    }
+    // 3x3 maxima of this thread's voxels: row maxima of the FT_VX + 2 rows they touch, then 3-row maxima; plane z = q - 1
+    // has its three planes once q > z0
+    float hM[FT_VX + 2];
+#pragma unroll
+    for (int rr = 0; rr < FT_VX + 2; ++rr) hM[rr] = max3v(M[FT_VX * hh + rr][cl], M[FT_VX * hh + rr][cc], M[FT_VX * hh + rr][cr]);
+    const int z = q - 1;
+    const double bound = q <= z0 ? 0.0 : smin ? lbs[z * ngz / Z][jb] : lb[((size_t)z * nbx + bx) * nby + (jb + by0)];
+#pragma unroll
+    for (int v = 0; v < FT_VX; ++v) {
+      const float P = max3v(hM[v], hM[v + 1], hM[v + 2]);
+      if (q == z0 - 1) { pp[v] = P; continue; }   // (uniform)
+      if (q > z0) {
+        const int x = x0 + FT_VX * hh + v;
+        const float vmax = __builtin_fmaxf(m2[v], P), cmax = cp[v];
+        bool hit = x < X && y < Y && (vmax == cmax) && ((double)cmax - bound >= th_test);
+        if (edge > 0)
+          hit = hit && z >= edge && z <= Z - edge && x >= edge && x <= X - edge && y >= edge && y <= Y - edge;
+        const unsigned long long ballot = __ballot(hit);
+        if (ballot) {
+          const int lane = t & 63;
+          unsigned basepos = 0;
+          if (lane == 0) basepos = atomicAdd(&ctl->n_cand, (unsigned)__popcll(ballot));
+          basepos = __shfl(basepos, 0);
+          if (hit) {
+            unsigned pos = basepos + (unsigned)__popcll(ballot & ((1ull << lane) - 1ull));
+            if (pos < capacity) out[pos] = Cand0{z, x, y, cmax};
+            else ctl->overflow = 1;
+          }
+        }
+      }
+      m2[v] = __builtin_fmaxf(pp[v], P); pp[v] = P; cp[v] = M[FT_VX * hh + v + 1][cc];   // (an in-image voxel's own row)
     }
   }
 }
@@ -876,6 +1058,8 @@ int g_strip_bound = 1;   // IA3_TUNE_SEED_STRIPS: 0 = block minima from a pass o
 void set_seed_strips(int on) { g_strip_bound = on ? 1 : 0; }
 int g_seed_dense = 0;   // IA3_TUNE_SEED_DENSE: 1 = always run the dense background filter (tests compare the two paths)
 void set_seed_dense(int on) { g_seed_dense = on ? 1 : 0; }
+int g_seed_fused = 1;   // IA3_TUNE_SEED_FUSED: 0 = plane-wise front filter into a stack + seed_cand3_tiled instead of seed_front_k
+void set_seed_fused(int on) { g_seed_fused = on ? 1 : 0; }
 
 constexpr unsigned LAZY_CAP = 1u << 17;   // first-stage candidates of the lazy background path (2 MB)
 
@@ -895,7 +1079,7 @@ static void launch_lazy(const void* mx, const void* zp, int Z, int X, int Y, con
   float* bmin = (float*)bnd;
   float* babs = bmin + nb;
   double* lb = lazy_bound_ptr(bnd, nb);
-  if (stage == 0) {   // needs only the axis-0 result: queued before the front filter is joined
+  if (stage == 0) {   // needs only the axis-0 result: queued before the front filter is joined (stage 2: the candidates are there)
     ProfScope ps("seed_blockmin");
     constexpr int V = 16 / (int)sizeof(T);
     const bool wide = Y % V == 0 && ((uintptr_t)zp & 15) == 0;   // every row starts on a 16-byte boundary
@@ -909,7 +1093,7 @@ static void launch_lazy(const void* mx, const void* zp, int Z, int X, int Y, con
                        Z, nbx, nby, (int)(sizeof(T) == 2), lb);
     return;
   }
-  {
+  if (stage == 1) {
     ProfScope ps("seed_detect");
     constexpr int ZT = 32;   // planes per block: two chunks of a 50-plane stack balance the skipped planes better than one (0.174 -> 0.164 ms)
     const unsigned tiles = (unsigned)((Y + 63) / 64) * (unsigned)((X + 15) / 16);
@@ -933,6 +1117,29 @@ static void launch_lazy(const void* mx, const void* zp, int Z, int X, int Y, con
     hipLaunchKernelGGL((bg_sparse_k<T>), dim3(4096), dim3(576), 0, s, (const T*)zp, Z, X, Y, t, R, IA3_MODE_REFLECT,
                        (const Cand0*)c0, (const SeedCtl*)ctl0, LAZY_CAP, th_low, out, capacity, ctl);
   }
+}
+
+// seed_front_k on the short filter's axis-0 result `in` (front taps w, radius 3): Cand0 list of the lazy background filter
+constexpr int FRONT_ZCHUNKS = 2;   // plane chunks per tile, one halo plane on either side: 2 x 2048 blocks for a 2048 x 2048 plane
+template <class T>
+static int launch_front(const void* in, const double* w, int Z, int X, int Y, int edge, double th_low, void* bnd,
+                        const float* smin, const float* sabs, Cand0* c0, SeedCtl* ctl0, hipStream_t s) {
+  ProfScope ps("seed_front_detect");
+  const int ntx = (X + FT_X - 1) / FT_X, nty = (Y + FT_Y - 1) / FT_Y;
+  const int* mxr = reflect_map(ntx * FT_X + 8, 4, X);   // positions -4 .. ntx * FT_X + 3
+  const int* myr = reflect_map(nty * FT_Y + 8, 4, Y);
+  if (!mxr || !myr) return set_error(IA3_ENOMEM, "border maps");
+  Taps3 tp;
+  for (int j = 0; j < 4; ++j) tp.w[j] = w[3 + j];
+  const int nbx = (X + 31) / 32, nby = (Y + 31) / 32;   // the bound's 32 x 32 blocks (background radius 30)
+  const double* lb = lazy_bound_ptr(bnd, (size_t)Z * nbx * nby);
+  const int zc = (Z + FRONT_ZCHUNKS - 1) / FRONT_ZCHUNKS;
+  const unsigned tiles = (unsigned)ntx * (unsigned)nty;
+  dim3 g(8 * ((tiles + 7) / 8), 1, (unsigned)((Z + zc - 1) / zc));   // tiles, XCD-grouped inside the kernel
+  const double th_test = th_low - fabs(th_low) * 1e-6 - 1e-300;   // as launch_lazy
+  hipLaunchKernelGGL((seed_front_k<T>), g, dim3(256), 0, s, (const T*)in, mxr, myr, tp, Z, X, Y, zc, edge, th_test, lb, smin, sabs,
+                     (int)DOG_PAIR_ZGROUPS, c0, LAZY_CAP, ctl0);
+  return IA3_OK;
 }
 
 static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut& out, SeedDev* dev, bool force_dense = false) {
@@ -1003,23 +1210,26 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
   int sm_ty = 0, sm_ntile = 0;
   size_t sm_count = 0;
   dog_pair_tiles(X, Y, &sm_ty, &sm_ntile, &sm_count);
-  Scratch smaxbuf(lazy ? sm_count * (size_t)Z * sizeof(float) : 256);   // step maxima of max_im (plane-wise filter -> detector)
+  const bool want_fused = lazy && g_seed_fused;
+  Scratch smaxbuf(lazy && !want_fused ? sm_count * (size_t)Z * sizeof(float) : 256);   // step maxima of max_im (plane-wise filter -> detector)
   if (!smaxbuf.p) return IA3_ENOMEM;
   const size_t n_strip = (lazy && Bk == 32) ? dog_pair_strips(X, Y) : 0;   // strip minima of the axis-0 result (column kernel -> bound)
   Scratch stripbuf(n_strip ? 2 * n_strip * sizeof(float) : 256);
   if (!stripbuf.p) return IA3_ENOMEM;
   float* smin_d = n_strip ? stripbuf.as<float>() : nullptr;
   float* sabs_d = n_strip ? smin_d + n_strip : nullptr;
-  bool forked = false, paired = false;
+  bool forked = false, paired = false, fused = false;
   if (p.gfilt_size > 0) {
     if (p.w_front) { w.assign(p.w_front, p.w_front + 2 * p.r_front + 1); R = p.r_front; }
     else gaussian_taps(p.gfilt_size, 4.0, w, R);
     if (lazy) {
       // short stacks: both axis-0 passes from one launch (the column is loaded once), then the short filter's other two
-      // axes on the auxiliary stream next to the block minima of the long filter's axis-0 result
+      // axes either inside the candidate test (seed_front_k, tmp2 = its input) or as a stack on the main stream next
+      // to the block minima of the long filter's axis-0 result
       int fk = 0;
-      rc = gauss_dog_pair(im->d, im->dtype, Z, X, Y, w.data(), R, wb.data(), Rb, a.p, b.p, tmp2.p, &fk, smaxbuf.as<float>(), smin_d, sabs_d);
-      if (rc == 0) { paired = true; forked = fk != 0; }
+      rc = gauss_dog_pair(im->d, im->dtype, Z, X, Y, w.data(), R, wb.data(), Rb, want_fused ? nullptr : a.p, b.p, tmp2.p, &fk,
+                          smaxbuf.as<float>(), smin_d, sabs_d);
+      if (rc == 0) { paired = true; forked = fk != 0; fused = want_fused; }
       else if (rc != 1) { if (fk) aux_join(); return rc; }
     }
     if (!paired) {
@@ -1032,7 +1242,14 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
     }
     maxim = a.p;
   }
-  if (paired) {
+  if (paired && fused) {
+    // nothing to run beside: the bound comes from the strip minima inside seed_front_k, or from a block-minimum pass
+    minim = b.p;
+    if (!(n_strip && g_strip_bound)) {
+      if (im->dtype == IA3_F32) launch_lazy<float>(nullptr, b.p, Z, X, Y, wb.data(), Rb, 0, 0, bnd.p, nullptr, nullptr, nullptr, 0, nullptr, s, 0);
+      else launch_lazy<uint16_t>(nullptr, b.p, Z, X, Y, wb.data(), Rb, 0, 0, bnd.p, nullptr, nullptr, nullptr, 0, nullptr, s, 0);
+    }
+  } else if (paired) {
     minim = b.p;
     // beside the plane-wise filter (main stream): the clears and the bound, on the auxiliary stream when there is one
     std::unique_ptr<AuxResume> ar(forked ? new AuxResume() : nullptr);
@@ -1076,7 +1293,17 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
     SeedCtl* dlazy = dctl + 1;
     Cand* dcand = (Cand*)((char*)bp + HDR);
     if (attempt > 0) IA3_HIP(hipMemsetAsync(dctl, 0, HDR, s));
-    if (lazy) {
+    if (fused) {
+      const float* sm = (n_strip && g_strip_bound) ? smin_d : nullptr;
+      if (im->dtype == IA3_F32) {
+        rc = launch_front<float>(tmp2.p, w.data(), Z, X, Y, p.min_edge_distance, th_low, bnd.p, sm, sabs_d, c0buf.as<Cand0>(), dlazy, s);
+        if (!rc) launch_lazy<float>(nullptr, b.p, Z, X, Y, wb.data(), Rb, p.min_edge_distance, th_low, bnd.p, c0buf.as<Cand0>(), dlazy, dcand, capacity, dctl, s, 2);
+      } else {
+        rc = launch_front<uint16_t>(tmp2.p, w.data(), Z, X, Y, p.min_edge_distance, th_low, bnd.p, sm, sabs_d, c0buf.as<Cand0>(), dlazy, s);
+        if (!rc) launch_lazy<uint16_t>(nullptr, b.p, Z, X, Y, wb.data(), Rb, p.min_edge_distance, th_low, bnd.p, c0buf.as<Cand0>(), dlazy, dcand, capacity, dctl, s, 2);
+      }
+      if (rc) return rc;
+    } else if (lazy) {
       if (im->dtype == IA3_F32)
         launch_lazy<float>(maxim, b.p, Z, X, Y, wb.data(), Rb, p.min_edge_distance, th_low, bnd.p, c0buf.as<Cand0>(), dlazy, dcand, capacity, dctl, s, 1,
                            paired ? smaxbuf.as<float>() : nullptr, sm_ty, sm_ntile);

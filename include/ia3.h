@@ -124,6 +124,11 @@ int ia3_profile_collect(char* buf, int len); /* "kernel,count,total_ms\n" lines 
  * seed is marked converged, as the reference's loop does after repeating it (External/Fitting_v4.py:651-680); 0 = every
  * refit is run.  Tables and sweep counts are identical bit for bit; the evaluation counters count the fits that ran. */
 #define IA3_TUNE_FIT_MEMO 14
+/* IA3_TUNE_SEED_FUSED: 1 (default) = where get_seeds pairs the two axis-0 passes in one column kernel (short filter of
+ * radius 3, background radius 30, a folded stack depth), one kernel runs the short filter's axis-1 and axis-2 passes and
+ * the 3x3x3 candidate test on tiles held in LDS: the front-filtered stack is never stored; 0 = the plane-wise filter
+ * writes it and the tiled detector reads it back.  Seeds are identical bit for bit. */
+#define IA3_TUNE_SEED_FUSED 15
 /* IA3_DEBUG_FIT_MAXFEV: PROFILING ONLY, changes results: > 0 caps the function evaluations of every fit (MINPACK's maxfev),
  * which splits the fit kernel's time into its fixed and its per-evaluation part; 0 (default) = the reference's limits. */
 #define IA3_DEBUG_FIT_MAXFEV 100
