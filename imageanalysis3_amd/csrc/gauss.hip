@@ -611,7 +611,7 @@ const int* cached_border_map(int count, int R, int len, int mode) {
 
 template <class T>
 int dog_pair_t(const T* src, int Z, int X, int Y, const Taps& ft, const Taps& bt, T* dst_front, T* dst_zp, T* tmp, hipStream_t s,
-               float* tmax, float* smin, float* sabs) {
+               float* tmax, float* smin, float* sabs, float* smx) {
   constexpr int RF = 3, RB = 30;
   const size_t plane = (size_t)X * Y;
   bool nonneg = true;
@@ -621,8 +621,8 @@ int dog_pair_t(const T* src, int Z, int X, int Y, const Taps& ft, const Taps& bt
   {
     ia3rt::ProfScope ps("gauss_axis0_pair");
     static_assert(RF == 3 && RB == 30, "the radii gauss_col.inc instantiates");
-    if constexpr (std::is_same_v<T, float>) rc = folded_pair_f32(src, Z, plane, bt, dst_zp, ft, tmp, s, cert, smin, sabs, Y);
-    else rc = folded_pair_u16(src, Z, plane, bt, dst_zp, ft, tmp, s, cert, smin, sabs, Y);
+    if constexpr (std::is_same_v<T, float>) rc = folded_pair_f32(src, Z, plane, bt, dst_zp, ft, tmp, s, cert, smin, sabs, Y, smx);
+    else rc = folded_pair_u16(src, Z, plane, bt, dst_zp, ft, tmp, s, cert, smin, sabs, Y, smx);
   }
   if (rc) return rc;   // FOLD_NOT_COVERED, or an error (negative)
   if (!dst_front) return FOLD_NO_FORK;   // the caller runs axes 1 and 2 of the short filter on tmp itself (seed_front_k)
@@ -853,8 +853,9 @@ void dog_pair_tiles(int X, int Y, int* ty, int* ntile, size_t* count) {
 size_t dog_pair_strips(int X, int Y) { return Y % 32 == 0 ? (size_t)DOG_PAIR_ZGROUPS * X * (Y / 32) : 0; }
 
 int gauss_dog_pair(const void* src, int dtype, int Z, int X, int Y, const double* wf, int rf, const double* wb, int rb,
-                   void* dst_front, void* dst_zp, void* tmp, int* forked, float* tmax, float* smin, float* sabs) {
-  if (Y % 32 != 0) smin = sabs = nullptr;   // strips are aligned groups of 32 lanes (callers check dog_pair_strips first)
+                   void* dst_front, void* dst_zp, void* tmp, int* forked, float* tmax, float* smin, float* sabs, float* smx) {
+  if (Y % 32 != 0) smin = sabs = nullptr;
+  if (!smin) smx = nullptr;                 // same condition   // strips are aligned groups of 32 lanes (callers check dog_pair_strips first)
   *forked = 0;
   if (!g_fold_on || rf != 3 || rb != 30 || !fold_depth(Z) || (size_t)Z * X * Y * (dtype == IA3_F32 ? 4 : 2) >= 0x7fffffffULL || Y < 8 || X < 4) return 1;
   for (int j = 1; j <= rf; ++j) if (wf[rf + j] != wf[rf - j]) return 1;
@@ -863,8 +864,8 @@ int gauss_dog_pair(const void* src, int dtype, int Z, int X, int Y, const double
   for (int j = 0; j < 64; ++j) { ft.w[j] = j <= rf ? wf[rf + j] : 0.0; bt.w[j] = j <= rb ? wb[rb + j] : 0.0; }
   hipStream_t s = ia3rt::stream();
   int rc;
-  if (dtype == IA3_F32) rc = dog_pair_t<float>((const float*)src, Z, X, Y, ft, bt, (float*)dst_front, (float*)dst_zp, (float*)tmp, s, tmax, smin, sabs);
-  else rc = dog_pair_t<uint16_t>((const uint16_t*)src, Z, X, Y, ft, bt, (uint16_t*)dst_front, (uint16_t*)dst_zp, (uint16_t*)tmp, s, tmax, smin, sabs);
+  if (dtype == IA3_F32) rc = dog_pair_t<float>((const float*)src, Z, X, Y, ft, bt, (float*)dst_front, (float*)dst_zp, (float*)tmp, s, tmax, smin, sabs, smx);
+  else rc = dog_pair_t<uint16_t>((const uint16_t*)src, Z, X, Y, ft, bt, (uint16_t*)dst_front, (uint16_t*)dst_zp, (uint16_t*)tmp, s, tmax, smin, sabs, smx);
   if (rc < 0) return rc;                       // IA3 error codes are negative: the filtered stacks were not produced
   if (rc == FOLD_NOT_COVERED) return 1;
   *forked = rc == 0;                           // FOLD_NO_FORK: queued on the main stream, nothing to join
@@ -909,6 +910,7 @@ int ia3_set_tuning(int key, int value) {
   if (key == IA3_TUNE_SEED_DENSE) { ia3k::set_seed_dense(value); return 0; }
   if (key == IA3_TUNE_SEED_STRIPS) { ia3k::set_seed_strips(value); return 0; }
   if (key == IA3_TUNE_SEED_FUSED) { ia3k::set_seed_fused(value); return 0; }
+  if (key == IA3_TUNE_SEED_SKIP) { ia3k::set_seed_skip(value); return 0; }
   if (key == IA3_TUNE_FIT_NBLIST) { ia3k::set_fit_nblist(value); return 0; }
   if (key == IA3_TUNE_FFT_C2C) { ia3k::set_fft_c2c(value); return 0; }
   if (key == IA3_TUNE_FIT_FUSE) { ia3k::set_fit_fuse(value); return 0; }

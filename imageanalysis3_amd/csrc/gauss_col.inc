@@ -59,18 +59,18 @@ int run_folded(const T* src, size_t plane, const Taps& t, int mode, T* dst, hipS
   const double* wf = folded_rows<Z, R>(t, mode, s);
   if (!wf) return ia3rt::set_error(IA3_ENOMEM, "folded weight table");
   hipLaunchKernelGGL((gauss_axis0_folded<T, Z, R, 0>), dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, src, dst, plane, wf, t, mode, cert,
-                     (T*)nullptr, t, (float*)nullptr, (float*)nullptr, 0);
+                     (T*)nullptr, t, (float*)nullptr, (float*)nullptr, 0, (float*)nullptr);
   return 0;
 }
 
 // both first passes of the DoG pair in one launch (long: folded, -> dst; short: radius RF, reflect, -> fdst)
 template <class T, int Z, int R, int RF>
 int run_folded_pair(const T* src, size_t plane, const Taps& t, T* dst, const Taps& ft, T* fdst, hipStream_t s, int cert,
-                    float* smin, float* sabs, int Y) {
+                    float* smin, float* sabs, int Y, float* smx) {
   const double* wf = folded_rows<Z, R>(t, IA3_MODE_REFLECT, s);
   if (!wf) return ia3rt::set_error(IA3_ENOMEM, "folded weight table");
   hipLaunchKernelGGL((gauss_axis0_folded<T, Z, R, RF>), dim3((unsigned)((plane + 255) / 256)), dim3(256), 0, s, src, dst, plane, wf, t,
-                     (int)IA3_MODE_REFLECT, cert, fdst, ft, smin, sabs, Y);
+                     (int)IA3_MODE_REFLECT, cert, fdst, ft, smin, sabs, Y, smx);
   return 0;
 }
 
@@ -90,8 +90,8 @@ int IA3_CAT3(folded_axis0, IA3_COL_SUFFIX, IA3_CAT(_z, IA3_COL_Z))(const IA3_COL
 }
 
 int IA3_CAT3(folded_pair, IA3_COL_SUFFIX, IA3_CAT(_z, IA3_COL_Z))(const IA3_COL_T* src, size_t plane, const Taps& bt, IA3_COL_T* dst, const Taps& ft,
-                                                                  IA3_COL_T* fdst, hipStream_t s, int cert, float* smin, float* sabs, int Y) {
-  return run_folded_pair<IA3_COL_T, IA3_COL_Z, 30, 3>(src, plane, bt, dst, ft, fdst, s, cert, smin, sabs, Y);
+                                                                  IA3_COL_T* fdst, hipStream_t s, int cert, float* smin, float* sabs, int Y, float* smx) {
+  return run_folded_pair<IA3_COL_T, IA3_COL_Z, 30, 3>(src, plane, bt, dst, ft, fdst, s, cert, smin, sabs, Y, smx);
 }
 
 }  // namespace ia3g

@@ -20,8 +20,8 @@ namespace ia3g {
 #define IA3_DECL(ZZ)                                                                                                        \
   int folded_axis0_f32_z##ZZ(const float*, size_t, const Taps&, int, float*, hipStream_t, int);                             \
   int folded_axis0_u16_z##ZZ(const uint16_t*, size_t, const Taps&, int, uint16_t*, hipStream_t, int);                       \
-  int folded_pair_f32_z##ZZ(const float*, size_t, const Taps&, float*, const Taps&, float*, hipStream_t, int, float*, float*, int);   \
-  int folded_pair_u16_z##ZZ(const uint16_t*, size_t, const Taps&, uint16_t*, const Taps&, uint16_t*, hipStream_t, int, float*, float*, int);
+  int folded_pair_f32_z##ZZ(const float*, size_t, const Taps&, float*, const Taps&, float*, hipStream_t, int, float*, float*, int, float*);   \
+  int folded_pair_u16_z##ZZ(const uint16_t*, size_t, const Taps&, uint16_t*, const Taps&, uint16_t*, hipStream_t, int, float*, float*, int, float*);
 IA3_FOLD_DEPTHS(IA3_DECL)
 #undef IA3_DECL
 
@@ -89,7 +89,7 @@ const double* rtc_rows_locked(int Z, const Taps& t, int mode) {
 }
 
 int rtc_launch(bool f32, int Z, const void* src, size_t plane, const Taps& t, int mode, void* dst, const Taps& ft, void* fdst, hipStream_t s,
-               int cert, float* smin, float* sabs, int Y, bool pair) {
+               int cert, float* smin, float* sabs, int Y, float* smx, bool pair) {
   hipFunction_t fn;
   const double* wf;
   {
@@ -100,10 +100,10 @@ int rtc_launch(bool f32, int Z, const void* src, size_t plane, const Taps& t, in
     if (!wf) return ia3rt::set_error(IA3_ENOMEM, "folded weight table");
     fn = pair ? d->pair : d->axis0;
   }
-  // (const T* in, T* out, size_t plane, const double* wf, Taps taps, int mode, int cert, T* fout, Taps ftaps, float* smin, float* sabs, int Y)
+  // (const T* in, T* out, size_t plane, const double* wf, Taps taps, int mode, int cert, T* fout, Taps ftaps, float* smin, float* sabs, int Y, float* smx)
   Taps ta = t, tb = ft;
   void* args[] = {(void*)&src, (void*)&dst, (void*)&plane, (void*)&wf, (void*)&ta, (void*)&mode, (void*)&cert, (void*)&fdst, (void*)&tb,
-                  (void*)&smin, (void*)&sabs, (void*)&Y};
+                  (void*)&smin, (void*)&sabs, (void*)&Y, (void*)&smx};
   if (hipModuleLaunchKernel(fn, (unsigned)((plane + 255) / 256), 1, 1, 256, 1, 1, 0, s, args, nullptr) != hipSuccess)
     return ia3rt::set_error(IA3_EHIP, "launch of the run-time compiled column kernel (depth %d) failed: %s", Z, hipGetErrorString(hipGetLastError()));
   return 0;
@@ -117,7 +117,7 @@ int folded_axis0_f32(const float* src, int Z, size_t plane, const Taps& t, int m
 #define IA3_FOLD_CASE(ZZ) case ZZ: return folded_axis0_f32_z##ZZ(src, plane, t, mode, dst, s, cert);
     IA3_FOLD_DEPTHS(IA3_FOLD_CASE)
 #undef IA3_FOLD_CASE
-    default: return rtc_launch(true, Z, src, plane, t, mode, dst, t, nullptr, s, cert, nullptr, nullptr, 0, false);
+    default: return rtc_launch(true, Z, src, plane, t, mode, dst, t, nullptr, s, cert, nullptr, nullptr, 0, nullptr, false);
   }
 }
 int folded_axis0_u16(const uint16_t* src, int Z, size_t plane, const Taps& t, int mode, uint16_t* dst, hipStream_t s, int cert) {
@@ -125,25 +125,25 @@ int folded_axis0_u16(const uint16_t* src, int Z, size_t plane, const Taps& t, in
 #define IA3_FOLD_CASE(ZZ) case ZZ: return folded_axis0_u16_z##ZZ(src, plane, t, mode, dst, s, cert);
     IA3_FOLD_DEPTHS(IA3_FOLD_CASE)
 #undef IA3_FOLD_CASE
-    default: return rtc_launch(false, Z, src, plane, t, mode, dst, t, nullptr, s, cert, nullptr, nullptr, 0, false);
+    default: return rtc_launch(false, Z, src, plane, t, mode, dst, t, nullptr, s, cert, nullptr, nullptr, 0, nullptr, false);
   }
 }
 int folded_pair_f32(const float* src, int Z, size_t plane, const Taps& bt, float* dst, const Taps& ft, float* fdst, hipStream_t s, int cert,
-                    float* smin, float* sabs, int Y) {
+                    float* smin, float* sabs, int Y, float* smx) {
   switch (Z) {
-#define IA3_FOLD_CASE(ZZ) case ZZ: return folded_pair_f32_z##ZZ(src, plane, bt, dst, ft, fdst, s, cert, smin, sabs, Y);
+#define IA3_FOLD_CASE(ZZ) case ZZ: return folded_pair_f32_z##ZZ(src, plane, bt, dst, ft, fdst, s, cert, smin, sabs, Y, smx);
     IA3_FOLD_DEPTHS(IA3_FOLD_CASE)
 #undef IA3_FOLD_CASE
-    default: return rtc_launch(true, Z, src, plane, bt, IA3_MODE_REFLECT, dst, ft, fdst, s, cert, smin, sabs, Y, true);
+    default: return rtc_launch(true, Z, src, plane, bt, IA3_MODE_REFLECT, dst, ft, fdst, s, cert, smin, sabs, Y, smx, true);
   }
 }
 int folded_pair_u16(const uint16_t* src, int Z, size_t plane, const Taps& bt, uint16_t* dst, const Taps& ft, uint16_t* fdst, hipStream_t s,
-                    int cert, float* smin, float* sabs, int Y) {
+                    int cert, float* smin, float* sabs, int Y, float* smx) {
   switch (Z) {
-#define IA3_FOLD_CASE(ZZ) case ZZ: return folded_pair_u16_z##ZZ(src, plane, bt, dst, ft, fdst, s, cert, smin, sabs, Y);
+#define IA3_FOLD_CASE(ZZ) case ZZ: return folded_pair_u16_z##ZZ(src, plane, bt, dst, ft, fdst, s, cert, smin, sabs, Y, smx);
     IA3_FOLD_DEPTHS(IA3_FOLD_CASE)
 #undef IA3_FOLD_CASE
-    default: return rtc_launch(false, Z, src, plane, bt, IA3_MODE_REFLECT, dst, ft, fdst, s, cert, smin, sabs, Y, true);
+    default: return rtc_launch(false, Z, src, plane, bt, IA3_MODE_REFLECT, dst, ft, fdst, s, cert, smin, sabs, Y, smx, true);
   }
 }
 

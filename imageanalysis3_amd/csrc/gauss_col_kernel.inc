@@ -41,6 +41,14 @@ template <int Z, int R> struct FoldTab {
 };
 template <int Z, int R> inline constexpr FoldTab<Z, R> fold_tab{};
 
+// order-preserving integer key of a stored value and back (strip maxima of the short pass, below)
+template <class T> __device__ __forceinline__ int mx_key(T q);
+template <> __device__ __forceinline__ int mx_key<float>(float q) { const int b = (int)__float_as_uint(q); return b ^ ((b >> 31) & 0x7fffffff); }
+template <> __device__ __forceinline__ int mx_key<uint16_t>(uint16_t q) { return (int)q; }
+template <class T> __device__ __forceinline__ float mx_val(int k);
+template <> __device__ __forceinline__ float mx_val<float>(int k) { return __uint_as_float((unsigned)(k ^ ((k >> 31) & 0x7fffffff))); }
+template <> __device__ __forceinline__ float mx_val<uint16_t>(int k) { return (float)k; }
+
 // RF > 0: the same launch also runs the axis-0 pass of a SHORT filter (radius RF, 'reflect' border) over the column
 // it holds and writes it to fout — the DoG seed detector filters one stack with a short and a long kernel, and the
 // two first passes share every load (NI_Correlate1D's sequence, unfused: the short pass is not a certified path).
@@ -48,7 +56,8 @@ template <class T, int Z, int R, int RF>
 __global__ __launch_bounds__(256) void gauss_axis0_folded(const T* __restrict__ in, T* __restrict__ out, size_t plane,
                                                           const double* __restrict__ wf, Taps taps, int mode, int cert,
                                                           T* __restrict__ fout, Taps ftaps,
-                                                          float* __restrict__ smin, float* __restrict__ sabs, int Y) {
+                                                          float* __restrict__ smin, float* __restrict__ sabs, int Y,
+                                                          float* __restrict__ smx) {
   // addressing: buffer descriptors, this thread's 32-bit byte offset in the plane + the plane's byte offset as the
   // scalar operand (the host checks Z * plane * sizeof(T) < 2^31): no vector address arithmetic per access
   const unsigned p = blockIdx.x * 256u + threadIdx.x;
@@ -79,24 +88,6 @@ __global__ __launch_bounds__(256) void gauss_axis0_folded(const T* __restrict__ 
     sbits |= sign_of<T>(t);
     v[z] = (double)t;
   }
-  if constexpr (RF > 0) {
-    static_assert(Z > RF, "single reflection");
-    const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)fout, (short)0, nbytes, 0x00020000);
-    auto frow = [&](auto zc) -> bool {
-      constexpr int z = decltype(zc)::value;
-      double acc = v[z] * ftaps.w[0];
-#pragma unroll
-      for (int j = RF; j >= 1; --j) {
-        const int lo = z - j < 0 ? -(z - j) - 1 : z - j, hi = z + j >= Z ? 2 * Z - 1 - (z + j) : z + j;   // compile-time
-        acc = acc + (v[lo] + v[hi]) * ftaps.w[j];
-      }
-      buf_st<T>(cvt<T>(acc), rf, voff, (unsigned)z * pbytes);
-      return true;
-    };
-    static_for_until<0, Z>(frow);
-    __builtin_amdgcn_sched_barrier(0);
-  }
-
   unsigned long long redo = 0;   // outputs that need NI_Correlate1D's own sequence (about one thread in 3e4 has one)
   const bool all = cert < 0 || (int)sbits < 0;
   if (all) redo = Z == 64 ? ~0ull : (1ull << Z) - 1;
@@ -150,6 +141,58 @@ __global__ __launch_bounds__(256) void gauss_axis0_folded(const T* __restrict__ 
     };
     static_for_until<0, NC>(piece);
   }
+  // The short pass runs BEHIND the long one: here no load is in flight, so the raw values no longer sit beside the column
+  // of doubles (in front of the long pass the strip maxima below took the kernel from 123 to 164 registers, three waves
+  // per SIMD instead of four, +0.1 ms; here it needs 124).
+  if constexpr (RF > 0) {
+    static_assert(Z > RF, "single reflection");
+    const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)fout, (short)0, nbytes, 0x00020000);
+    // smx (optional, with smin; the seed detector skips planes by it, ia3_seedskip.h): the largest STORED value of this
+    // short pass per plane, row and 32-column strip, [row][strip][plane, padded to ZP] floats.  The reduction runs on an
+    // order-preserving integer key (mx_key: integer max instructions take the lane rotations as DPP operands and need no
+    // NaN canonicalisation; fmaxf on rotated copies came to 25 instructions a plane and 164 registers against 123).  A
+    // NaN with the sign bit clear orders above +inf and comes out as NaN: the reader takes a NaN strip for +inf (live);
+    // one with the sign bit set orders below -inf and is left out, as fmaxf would.  32 lanes = two DPP rows: four
+    // rotations inside each row, then lane 15 of the lower row into the upper one (row_bcast15): every lane of the upper
+    // row holds the strip's maximum.  Lane 16 + k keeps that of plane 16 g + k, and the row stores 16 planes at once, in
+    // whole 64-byte pieces.
+    constexpr unsigned ZP = (Z + 15) & ~15;
+    const bool mx_row = (threadIdx.x & 16) != 0;
+    const unsigned lane15 = threadIdx.x & 15;
+    const unsigned mx_base = (p >> 5) * ZP + lane15;   // Y % 32 == 0: strip (row, column / 32) is p / 32; ZP * plane / 32 < 2^31
+    int keep = 0;
+    const bool want_mx = smx != nullptr;   // (uniform)
+    auto frow = [&](auto zc) -> bool {
+      constexpr int z = decltype(zc)::value;
+      double acc = v[z] * ftaps.w[0];
+#pragma unroll
+      for (int j = RF; j >= 1; --j) {
+        const int lo = z - j < 0 ? -(z - j) - 1 : z - j, hi = z + j >= Z ? 2 * Z - 1 - (z + j) : z + j;   // compile-time
+        acc = acc + (v[lo] + v[hi]) * ftaps.w[j];
+      }
+      const T qf = cvt<T>(acc);
+      buf_st<T>(qf, rf, voff, (unsigned)z * pbytes);
+      if (want_mx) {
+#define IA3_DPP(v, c) __builtin_amdgcn_update_dpp(0, (v), (c), 0xf, 0xf, true)
+        int k = mx_key<T>(qf), o;
+        o = IA3_DPP(k, 0x128); k = k > o ? k : o;   // row_ror:8
+        o = IA3_DPP(k, 0x124); k = k > o ? k : o;
+        o = IA3_DPP(k, 0x122); k = k > o ? k : o;
+        o = IA3_DPP(k, 0x121); k = k > o ? k : o;
+        o = IA3_DPP(k, 0x142); k = k > o ? k : o;   // row_bcast15 (the lower row reads 0: its lanes are not used)
+#undef IA3_DPP
+        keep = lane15 == (unsigned)(z & 15) ? k : keep;
+        if constexpr ((z & 15) == 15 || z == Z - 1) {
+          if (mx_row) smx[mx_base + (z & ~15)] = mx_val<T>(keep);
+        }
+      }
+      // two planes at a time: left alone, the scheduler interleaves all Z planes and the kernel comes to 339 registers
+      return true;
+    };
+    static_for_until<0, Z>(frow);
+    __builtin_amdgcn_sched_barrier(0);
+  }
+
   // NI_Correlate1D's own sequence, inputs re-read (a few outputs per 10^7 on non-negative data)
   // NI_Correlate1D's own sequence, inputs re-read from memory, all 2R+1 loads of an output in flight together
   while (redo) {

@@ -115,7 +115,7 @@ void gaussian_taps(double sigma, double truncate, std::vector<double>& w, int& r
 
 // ---- stage entry points implemented in the .hip files (device pointers, library stream) ------
 namespace ia3k { void set_dft_valu(int on); void set_fft_c2c(int on); void set_seed_dense(int on);
-void set_seed_strips(int on); void set_seed_fused(int on); void set_fit_nblist(int cap); void set_fit_fuse(int on); void set_fit_waves(int n); void set_fit_maxfev(int n); void set_fit_merge(int on); void set_warp_onepass(int v); void set_fit_kdq(int cap); void set_fit_memo(int on); int set_fit_waitbound(int polls); }   // fft_align.hip: test knob, see IA3_TUNE_DFT_VALU
+void set_seed_strips(int on); void set_seed_fused(int on); void set_seed_skip(int v); void set_fit_nblist(int cap); void set_fit_fuse(int on); void set_fit_waves(int n); void set_fit_maxfev(int n); void set_fit_merge(int on); void set_warp_onepass(int v); void set_fit_kdq(int cap); void set_fit_memo(int on); int set_fit_waitbound(int polls); }   // fft_align.hip: test knob, see IA3_TUNE_DFT_VALU
 namespace ia3k {
 // separable Gaussian along all three axes: src -> dst, tmp is a same-size scratch stack.  axes: bit 0 = the axis-0
 // pass (src -> dst), bit 1 = the axis-1 and axis-2 passes (dst -> tmp -> dst); radius <= 3 runs fused (axes == 3 only).
@@ -127,11 +127,13 @@ int highpass_combine(const void* im, const void* low, int dtype, size_t n, void*
 // tmax (optional): per plane, 16-row step and y tile (dog_pair_tiles) the largest value of dst_front, for the detector
 // smin / sabs (optional, dog_pair_strips(X, Y) floats each, only when that is non-zero): smallest value / largest magnitude
 // of dst_zp per group of planes (group of plane z = z * DOG_PAIR_ZGROUPS / Z), row and 32-column strip
+// smx (optional, with smin; X * (Y / 32) * ((Z + 15) & ~15) floats, [row][strip][plane, padded to a multiple of 16]): largest value of tmp (the short filter's axis-0
+// result) per plane, row and 32-column strip, for the plane skipping of the fused detector (ia3_seedskip.h)
 constexpr int DOG_PAIR_ZGROUPS = 5;
 size_t dog_pair_strips(int X, int Y);
 int gauss_dog_pair(const void* src, int dtype, int Z, int X, int Y, const double* wf, int rf, const double* wb, int rb,
                    void* dst_front, void* dst_zp, void* tmp, int* forked, float* tmax = nullptr, float* smin = nullptr,
-                   float* sabs = nullptr);
+                   float* sabs = nullptr, float* smx = nullptr);
 void dog_pair_tiles(int X, int Y, int* ty, int* ntile, size_t* count);
 // device map i -> scipy 'reflect' index of position i - R along an axis of length len (cached per process and device)
 const int* reflect_map(int count, int R, int len);

@@ -17,6 +17,7 @@
 // (8 B/voxel for f32) by an LDS-tiled kernel with a rolling three-plane register pipeline along z.
 #include "ia3_rt.h"
 #include "ia3_gauss_dev.h"
+#include "ia3_seedskip.h"
 #include <memory>
 #include <algorithm>
 #include <math.h>
@@ -497,6 +498,14 @@ __global__ __launch_bounds__(256) void seed_cand3_tiled(const T* __restrict__ mx
 // The input rows of the next plane are fetched as soon as the current plane's are in registers.
 // Bound: with strip minima (smin != nullptr) the block takes its <= 4 blocks' bounds for the chunk's plane groups from
 // them in a prologue (stripbound_k's reduction, one wave per 32-column block), otherwise it reads lb.
+// Skipping (smx != nullptr, with smin; at most 62 planes per chunk): max_im feeds nothing but the test, and the test
+// cannot pass where max_im stays below th_test + bound.  From the column kernel's strip maxima of `in` over the tile's
+// window (rows x0-3 .. x0+FT_X+2, and per 32-column strip of the tile that strip and its two neighbours; zp floats per
+// row and strip) the prologue
+// makes the certified bound of ia3_seedskip.h per plane and strip: a plane is LIVE when some strip of it can pass,
+// NEEDED when it or a z-neighbour is live.  Only needed planes are fetched, filtered and tested (block-uniform: their
+// barriers go with them), and only live planes are tested — a live plane's three planes are all needed, so the rolling
+// registers never carry a value across a gap into a test.  ctl->pad[0] counts the planes run (one atomic per block).
 constexpr int FT_X = 16, FT_Y = 128;
 constexpr int FT_AR = FT_X + 2, FT_AC = FT_Y + 8, FT_MC = FT_Y + 2, FT_MP = FT_Y + 4;   // A rows / columns, M columns / pitch
 constexpr int FT_R1 = FT_AR / 2;                 // axis-1 outputs per thread (two threads per column of A)
@@ -509,11 +518,13 @@ __global__ __launch_bounds__(256, 4) void seed_front_k(const T* __restrict__ in,
                                                     Taps3 taps, int Z, int X, int Y, int zc, int edge, double th_test,
                                                     const double* __restrict__ lb, const float* __restrict__ smin,
                                                     const float* __restrict__ sabs, int ngz, Cand0* __restrict__ out,
-                                                    unsigned capacity, SeedCtl* __restrict__ ctl) {
+                                                    unsigned capacity, SeedCtl* __restrict__ ctl,
+                                                    const float* __restrict__ smx, int zp, double sup) {
   static_assert(FT_Y == 128 && FT_X % 16 == 0 && 32 % FT_X == 0, "thread mapping below; a tile lies in one row of 32 x 32 bound blocks");
   __shared__ __attribute__((aligned(16))) float A[FT_AR][FT_AC];   // axis-1 result (a T value held in a float)
   __shared__ __attribute__((aligned(16))) float M[FT_AR][FT_MP];   // max_im
   __shared__ double lbs[ia3k::DOG_PAIR_ZGROUPS][FT_Y / 32];
+  __shared__ unsigned long long lvs;
   const int t = threadIdx.x;
   const int nty = (Y + FT_Y - 1) / FT_Y, ntx = (X + FT_X - 1) / FT_X;
   const int tile = xcd_tile(blockIdx.x, nty * ntx);
@@ -522,6 +533,20 @@ __global__ __launch_bounds__(256, 4) void seed_front_k(const T* __restrict__ in,
   const int z0 = blockIdx.z * zc, z1 = min(z0 + zc, Z);
   const int nby = (Y + 31) / 32, nbx = (X + 31) / 32, bx = x0 / 32, by0 = y0 / 32;
   const int is_u16 = sizeof(T) == 2;
+  // strip maxima of the tile's window, rows x0-3 .. x0+FT_X+2 (those inside the image): 32 lanes along the planes, one
+  // strip per group of 32 threads; the loads of the first 32 planes are in flight under the bound's prologue
+  const int sg = t >> 5, szi = t & 31;
+  auto skip_ld = [&](int zb, int k) -> float {
+    const int r = x0 - 3 + k, sb = by0 - 1 + sg;
+    const bool ok = sg < 6 && sb >= 0 && sb < nby && r >= 0 && r < X && zb + szi < z1 - z0;
+    const float v = ok ? smx[((size_t)r * nby + sb) * zp + z0 + zb + szi] : -INFINITY;
+    return v != v ? INFINITY : v;   // a strip that reports NaN (the column kernel: a NaN with the sign bit clear): live
+  };
+  float sv[FT_X + 6];
+  if (smx) {
+#pragma unroll
+    for (int k = 0; k < FT_X + 6; ++k) sv[k] = skip_ld(0, k);
+  }
   if (smin) {
     const int w = t >> 6, lane = t & 63;
     if (by0 + w < nby)   // whole wave
@@ -530,6 +555,49 @@ __global__ __launch_bounds__(256, 4) void seed_front_k(const T* __restrict__ in,
         if (lane == 0) lbs[g][w] = v;
       }
   }
+  // live planes of the chunk: bit j <-> plane z0 + j
+  const int npl = z1 - z0;
+  unsigned long long live = npl >= 64 ? ~0ull : (1ull << npl) - 1ull;
+  if (smx) {   // (uniform; the host gives it only with smin and npl <= 62)
+    static_assert(6 * 64 <= FT_AR * FT_AC, "the window maxima borrow A");
+    float* pm = &A[0][0];   // [strip by0-1 .. by0+4][plane]
+    for (int zb = 0; zb < npl; zb += 32) {
+      if (zb) {
+        float m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < FT_X + 6; ++k) m = fmaxf(m, skip_ld(zb, k));
+        if (sg < 6) pm[sg * 64 + zb + szi] = m;
+      } else {
+        float m = -INFINITY;
+#pragma unroll
+        for (int k = 0; k < FT_X + 6; ++k) m = fmaxf(m, sv[k]);
+        if (sg < 6) pm[sg * 64 + szi] = m;
+      }
+    }
+    __syncthreads();   // pm, lbs
+    if (t < 64) {   // wave 0
+      bool lv = false;
+      if (t < npl) {
+        float c[6];
+#pragma unroll
+        for (int j = 0; j < 6; ++j) c[j] = pm[j * 64 + t];
+        const int g = (z0 + t) * ngz / Z;
+#pragma unroll
+        for (int j = 0; j < FT_Y / 32; ++j)
+          if (by0 + j < nby)
+            lv = lv || ia3skip::unit_live(ia3skip::front_bound<sizeof(T) == 2>(fmaxf(fmaxf(c[j], c[j + 1]), c[j + 2]), sup), lbs[g][j], th_test);
+      }
+      const unsigned long long b = __ballot(lv);
+      if (t == 0) lvs = b;
+    }
+    __syncthreads();   // lvs; every read of pm is behind this barrier (A is written next)
+    live = lvs;
+    live = ((unsigned long long)__builtin_amdgcn_readfirstlane((unsigned)(live >> 32)) << 32) | __builtin_amdgcn_readfirstlane((unsigned)live);
+  }
+  // needed planes: bit i <-> plane q = z0 - 1 + i (the chunk's planes and one halo plane on either side)
+  unsigned long long rem = live | (live << 1) | (live << 2);
+  if (t == 0) atomicAdd(&ctl->pad[0], (unsigned)__popcll(rem));
+  if (!rem) return;   // whole block
   // addressing: buffer descriptors (the host checks that the stack is below 2^31 bytes); a thread's column offset is
   // fixed, the row offsets of the main pass are wave-uniform (scalar)
   const unsigned ES = (unsigned)sizeof(T), rowb = (unsigned)Y * ES, planeb = (unsigned)X * rowb;
@@ -579,16 +647,23 @@ __global__ __launch_bounds__(256, 4) void seed_front_k(const T* __restrict__ in,
   const int jb = min(y, Y - 1) / 32 - by0;
   const bool rfix0 = x0 == 0, rfix1 = X - x0 + 1 < FT_AR;   // M rows at positions -1 / X inside the tile
   float m2[FT_VX], pp[FT_VX], cp[FT_VX];   // max of the 3x3 maxima of planes q-2 and q-1, the 3x3 maximum of q-1, the centre of q-1
-  fetch(z0 - 1);
-  __syncthreads();   // lbs
-  for (int q = z0 - 1; q <= z1; ++q) {
+#pragma unroll
+  for (int v = 0; v < FT_VX; ++v) m2[v] = pp[v] = cp[v] = 0.f;   // (never read before three needed planes in a row have set them)
+  int i = __builtin_ctzll(rem);
+  rem &= rem - 1ull;
+  fetch(z0 - 1 + i);
+  if (!smx) __syncthreads();   // lbs
+  for (;;) {
+    const int q = z0 - 1 + i;
+    const int inx = rem ? __builtin_ctzll(rem) : -1;   // the next needed plane
+    rem &= rem - 1ull;
     {
       double v[FT_NIN], ve[8];
 #pragma unroll
       for (int i = 0; i < FT_NIN; ++i) v[i] = (double)nxt[i];
 #pragma unroll
       for (int i = 0; i < 8; ++i) ve[i] = (double)nxe[i];
-      if (q < z1) fetch(q + 1);   // in flight under the whole of this plane
+      if (inx >= 0) fetch(z0 - 1 + inx);   // in flight under the whole of this plane
 #pragma unroll
       for (int o = 0; o < FT_R1; ++o) A[h * FT_R1 + o][k] = a1(v + o);
       if (ex) {
@@ -629,12 +704,12 @@ __global__ __launch_bounds__(256, 4) void seed_front_k(const T* __restrict__ in,
 #pragma unroll
     for (int rr = 0; rr < FT_VX + 2; ++rr) hM[rr] = max3v(M[FT_VX * hh + rr][cl], M[FT_VX * hh + rr][cc], M[FT_VX * hh + rr][cr]);
     const int z = q - 1;
-    const double bound = q <= z0 ? 0.0 : smin ? lbs[z * ngz / Z][jb] : lb[((size_t)z * nbx + bx) * nby + (jb + by0)];
+    const bool tst = i >= 2 && ((live >> (i - 2)) & 1ull);   // (uniform) plane z is in the chunk and live
+    const double bound = !tst ? 0.0 : smin ? lbs[z * ngz / Z][jb] : lb[((size_t)z * nbx + bx) * nby + (jb + by0)];
 #pragma unroll
     for (int v = 0; v < FT_VX; ++v) {
       const float P = max3v(hM[v], hM[v + 1], hM[v + 2]);
-      if (q == z0 - 1) { pp[v] = P; continue; }   // (uniform)
-      if (q > z0) {
+      if (tst) {
         const int x = x0 + FT_VX * hh + v;
         const float vmax = __builtin_fmaxf(m2[v], P), cmax = cp[v];
         bool hit = x < X && y < Y && (vmax == cmax) && ((double)cmax - bound >= th_test);
@@ -655,6 +730,8 @@ __global__ __launch_bounds__(256, 4) void seed_front_k(const T* __restrict__ in,
       }
       m2[v] = __builtin_fmaxf(pp[v], P); pp[v] = P; cp[v] = M[FT_VX * hh + v + 1][cc];   // (an in-image voxel's own row)
     }
+    if (inx < 0) break;
+    i = inx;
   }
 }
 
@@ -983,8 +1060,10 @@ __global__ __launch_bounds__(256) void fin_scatter_k(const SeedCtl* __restrict__
   const unsigned ov = sctl->overflow | ((lazy && (lazy->overflow || lazy->n_cand > cap0)) ? 2u : 0u) | (fc->n_kept > FIN_KEYS ? 4u : 0u);
   fcw->n_cand = nc;
   fcw->overflow = ov;
+  fcw->pad[0] = lazy ? lazy->pad[0] : 0u;   // planes seed_front_k ran
   if (mail) {   // the four control words straight into the host's pinned mailbox, then the sequence number it polls
     mail[1] = fcw->n_alive; mail[2] = (unsigned)fcw->chosen; mail[3] = nc; mail[4] = ov;
+    mail[5] = fcw->pad[0];
     __threadfence_system();
     mail[0] = seq;
   }
@@ -1060,6 +1139,12 @@ int g_seed_dense = 0;   // IA3_TUNE_SEED_DENSE: 1 = always run the dense backgro
 void set_seed_dense(int on) { g_seed_dense = on ? 1 : 0; }
 int g_seed_fused = 1;   // IA3_TUNE_SEED_FUSED: 0 = plane-wise front filter into a stack + seed_cand3_tiled instead of seed_front_k
 void set_seed_fused(int on) { g_seed_fused = on ? 1 : 0; }
+// IA3_TUNE_SEED_SKIP: 0 = seed_front_k runs every plane of every tile (no strip maxima from the column kernel); 1 = it
+// skips dead planes; 2 (default) = and the first-stage list is made at the first dynamic level instead of the lowest
+int g_seed_skip = 2;
+void set_seed_skip(int v) { g_seed_skip = v < 0 ? 0 : (v > 2 ? 2 : v); }
+// (tile, plane) units of the calling thread's last seed stage: run by seed_front_k / in all (ia3_seed_skip_stats)
+static thread_local double t_skip_run = 0, t_skip_all = 0;
 
 constexpr unsigned LAZY_CAP = 1u << 17;   // first-stage candidates of the lazy background path (2 MB)
 
@@ -1121,9 +1206,12 @@ static void launch_lazy(const void* mx, const void* zp, int Z, int X, int Y, con
 
 // seed_front_k on the short filter's axis-0 result `in` (front taps w, radius 3): Cand0 list of the lazy background filter
 constexpr int FRONT_ZCHUNKS = 2;   // plane chunks per tile, one halo plane on either side: 2 x 2048 blocks for a 2048 x 2048 plane
+inline int front_zchunk(int Z) { return (Z + FRONT_ZCHUNKS - 1) / FRONT_ZCHUNKS; }
+// smx / sup: the column kernel's strip maxima of `in` and the taps' certified sum (ia3_seedskip.h), or nullptr: no plane is skipped
 template <class T>
 static int launch_front(const void* in, const double* w, int Z, int X, int Y, int edge, double th_low, void* bnd,
-                        const float* smin, const float* sabs, Cand0* c0, SeedCtl* ctl0, hipStream_t s) {
+                        const float* smin, const float* sabs, Cand0* c0, SeedCtl* ctl0, hipStream_t s,
+                        const float* smx, double sup) {
   ProfScope ps("seed_front_detect");
   const int ntx = (X + FT_X - 1) / FT_X, nty = (Y + FT_Y - 1) / FT_Y;
   const int* mxr = reflect_map(ntx * FT_X + 8, 4, X);   // positions -4 .. ntx * FT_X + 3
@@ -1133,17 +1221,21 @@ static int launch_front(const void* in, const double* w, int Z, int X, int Y, in
   for (int j = 0; j < 4; ++j) tp.w[j] = w[3 + j];
   const int nbx = (X + 31) / 32, nby = (Y + 31) / 32;   // the bound's 32 x 32 blocks (background radius 30)
   const double* lb = lazy_bound_ptr(bnd, (size_t)Z * nbx * nby);
-  const int zc = (Z + FRONT_ZCHUNKS - 1) / FRONT_ZCHUNKS;
+  const int zc = front_zchunk(Z);
+  if (!smin || zc > 62) smx = nullptr;   // the kernel's plane masks are 64 bits: the chunk and its two halo planes
   const unsigned tiles = (unsigned)ntx * (unsigned)nty;
   dim3 g(8 * ((tiles + 7) / 8), 1, (unsigned)((Z + zc - 1) / zc));   // tiles, XCD-grouped inside the kernel
   const double th_test = th_low - fabs(th_low) * 1e-6 - 1e-300;   // as launch_lazy
   hipLaunchKernelGGL((seed_front_k<T>), g, dim3(256), 0, s, (const T*)in, mxr, myr, tp, Z, X, Y, zc, edge, th_test, lb, smin, sabs,
-                     (int)DOG_PAIR_ZGROUPS, c0, LAZY_CAP, ctl0);
+                     (int)DOG_PAIR_ZGROUPS, c0, LAZY_CAP, ctl0, smx, (Z + 15) & ~15, sup);
+  t_skip_all = (double)tiles * (double)(Z + 2 * ((Z + zc - 1) / zc));   // every chunk's planes and its two halo planes
   return IA3_OK;
 }
 
-static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut& out, SeedDev* dev, bool force_dense = false) {
+static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut& out, SeedDev* dev, bool force_dense = false,
+                         bool low_list = false) {
   hipStream_t s = stream();
+  t_skip_run = t_skip_all = 0;
   const bool dbg = getenv("IA3_DEBUG_TIMING") != nullptr;
   const double t0 = now_ms();
   const int Z = im->Z, X = im->X, Y = im->Y;
@@ -1222,13 +1314,23 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
   if (p.gfilt_size > 0) {
     if (p.w_front) { w.assign(p.w_front, p.w_front + 2 * p.r_front + 1); R = p.r_front; }
     else gaussian_taps(p.gfilt_size, 4.0, w, R);
+  }
+  // plane skipping of the fused detector: strip maxima of the short filter's axis-0 result, only where the certificate
+  // holds (every front tap >= 0, ia3_seedskip.h) and the detector takes its bound from the strip minima
+  double skip_sup = 0.0;
+  const bool want_skip = want_fused && g_seed_skip && n_strip && g_strip_bound && p.gfilt_size > 0 && R == 3 &&
+                         front_zchunk(Z) <= 62 && ia3skip::taps_sup(w.data() + 3, &skip_sup);
+  Scratch smxbuf(want_skip ? (size_t)X * (Y / 32) * ((Z + 15) & ~15) * sizeof(float) : 256);
+  if (!smxbuf.p) return IA3_ENOMEM;
+  const float* smx_d = want_skip ? smxbuf.as<float>() : nullptr;
+  if (p.gfilt_size > 0) {
     if (lazy) {
       // short stacks: both axis-0 passes from one launch (the column is loaded once), then the short filter's other two
       // axes either inside the candidate test (seed_front_k, tmp2 = its input) or as a stack on the main stream next
       // to the block minima of the long filter's axis-0 result
       int fk = 0;
       rc = gauss_dog_pair(im->d, im->dtype, Z, X, Y, w.data(), R, wb.data(), Rb, want_fused ? nullptr : a.p, b.p, tmp2.p, &fk,
-                          smaxbuf.as<float>(), smin_d, sabs_d);
+                          smaxbuf.as<float>(), smin_d, sabs_d, want_skip ? smxbuf.as<float>() : nullptr);
       if (rc == 0) { paired = true; forked = fk != 0; fused = want_fused; }
       else if (rc != 1) { if (fk) aux_join(); return rc; }
     }
@@ -1278,6 +1380,14 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
   rc = clear_buffers();
   if (rc) { if (forked) aux_join(); return rc; }
   if (forked) { rc = aux_join(); if (rc) return rc; }
+  // The reference lowers the threshold only when a level yields fewer than min_dynamic_seeds seeds, so on an image that has
+  // spots the result is the list at level 0.  The fused path therefore makes its first-stage list at th[0] when that is
+  // the largest level (fewer live planes for seed_front_k, fewer candidates for the sparse background pass): the count at
+  // level 0 is exact, so the finish picks level 0 exactly when the reference does; if it picks another level, the seed
+  // stage starts over with the lowest level as list threshold (low_list), as it does after an overflow.
+  bool top_list = !low_list && fused && g_seed_skip >= 2 && lev.n > 1 && lev.th[0] > th_low;
+  for (int i = 1; i < lev.n; ++i) top_list = top_list && lev.th[0] >= lev.th[i];
+  const double th_list = top_list ? lev.th[0] : th_low;
   const double t1 = now_ms();
   // device buffer = [SeedCtl out | SeedCtl lazy | Cand x capacity]; the header and the first FIRST candidates come back
   // in ONE copy (the common case: a few thousand seeds), the rest only if there are more
@@ -1294,12 +1404,13 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
     Cand* dcand = (Cand*)((char*)bp + HDR);
     if (attempt > 0) IA3_HIP(hipMemsetAsync(dctl, 0, HDR, s));
     if (fused) {
+      const double th_low = th_list;   // (the fused path's list threshold, see top_list)
       const float* sm = (n_strip && g_strip_bound) ? smin_d : nullptr;
       if (im->dtype == IA3_F32) {
-        rc = launch_front<float>(tmp2.p, w.data(), Z, X, Y, p.min_edge_distance, th_low, bnd.p, sm, sabs_d, c0buf.as<Cand0>(), dlazy, s);
+        rc = launch_front<float>(tmp2.p, w.data(), Z, X, Y, p.min_edge_distance, th_low, bnd.p, sm, sabs_d, c0buf.as<Cand0>(), dlazy, s, smx_d, skip_sup);
         if (!rc) launch_lazy<float>(nullptr, b.p, Z, X, Y, wb.data(), Rb, p.min_edge_distance, th_low, bnd.p, c0buf.as<Cand0>(), dlazy, dcand, capacity, dctl, s, 2);
       } else {
-        rc = launch_front<uint16_t>(tmp2.p, w.data(), Z, X, Y, p.min_edge_distance, th_low, bnd.p, sm, sabs_d, c0buf.as<Cand0>(), dlazy, s);
+        rc = launch_front<uint16_t>(tmp2.p, w.data(), Z, X, Y, p.min_edge_distance, th_low, bnd.p, sm, sabs_d, c0buf.as<Cand0>(), dlazy, s, smx_d, skip_sup);
         if (!rc) launch_lazy<uint16_t>(nullptr, b.p, Z, X, Y, wb.data(), Rb, p.min_edge_distance, th_low, bnd.p, c0buf.as<Cand0>(), dlazy, dcand, capacity, dctl, s, 2);
       }
       if (rc) return rc;
@@ -1360,14 +1471,18 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
           }
         }
         hfc.n_alive = mb[1]; hfc.chosen = (int)mb[2]; hfc.n_cand = mb[3]; hfc.overflow = mb[4];
+        if (fused) t_skip_run = (double)mb[5];
         dbg_stamp("seed count seen");
       } else {
         if (fe == hipSuccess) fe = hipMemcpyAsync(&hfc, fc, sizeof(FinCtl), hipMemcpyDeviceToHost, s);
         if (fe == hipSuccess) fe = hipStreamSynchronize(s);
+        if (fe == hipSuccess && fused) t_skip_run = (double)hfc.pad[0];
       }
       if (fe != hipSuccess) return set_error(IA3_EHIP, "seed finish failed: %s", hipGetErrorString(fe));
       if (hfc.overflow & 2u)     // more first-stage candidates than the lazy path is sized for: dense filter instead
         return dog_seed_impl(im, p, out, dev, true);
+      if (top_list && hfc.chosen != 0)   // level 0 has too few seeds: the list at th[0] does not hold the other levels' seeds
+        return dog_seed_impl(im, p, out, dev, force_dense, true);
       hctl.n_cand = hfc.n_cand; hctl.overflow = hfc.overflow;
       if (hctl.n_cand <= FIN_CAP && !hctl.overflow) {
         int n = (int)hfc.n_alive;
@@ -1390,6 +1505,7 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
     IA3_HIP(hipStreamSynchronize(s));
     memcpy(&hctl, hbuf.data(), sizeof(SeedCtl));
     memcpy(&hlazy, hbuf.data() + sizeof(SeedCtl), sizeof(SeedCtl));
+    if (fused) t_skip_run = (double)hlazy.pad[0];
     if (lazy && (hlazy.overflow || hlazy.n_cand > LAZY_CAP)) return dog_seed_impl(im, p, out, dev, true);
     if (hctl.n_cand <= capacity) {
       cand.resize(hctl.n_cand);
@@ -1406,6 +1522,7 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
   }
   const double t2 = now_ms();
   finish_seeds(cand, lev, p, Y, out);
+  if (top_list && out.th_used != lev.th[0]) return dog_seed_impl(im, p, out, dev, force_dense, true);
   if (dbg) fprintf(stderr, "dog_seed: launch gauss %.3f ms, detect+copy(sync) %.3f ms, finish %.3f ms (%zu cand)\n", t1 - t0, t2 - t1, now_ms() - t2, cand.size());
   return IA3_OK;
 }
@@ -1615,6 +1732,12 @@ int ia3_seed_in_distance(const void* im, int dtype, int Z, int X, int Y, const d
   return IA3_OK;
 }
 
+
+int ia3_seed_skip_stats(double* out2) {
+  if (!out2) return set_error(IA3_EINVAL, "null output");
+  out2[0] = ia3k::t_skip_run; out2[1] = ia3k::t_skip_all;
+  return IA3_OK;
+}
 
 int ia3_dog_seed_dev(const ia3_stack* im, const ia3_seed_params* p, double* out_zxyh, int capacity,
                      int* n_out, double* th_used) {

@@ -62,6 +62,9 @@ int ia3_prepare_depth(int dtype, int Z);
 /* the scratch cache: out6 = {idle bytes, bytes in use, blocks, hipMalloc calls, hipFree calls, ms spent in both} since
    the library was loaded; a steady-state loop adds no calls (each hipFree synchronises the device) */
 int ia3_workspace_stats(double* out6);
+/* the fused seed detector's (tile, plane) units of the calling thread's last get_seeds: out2 = {units filtered and tested,
+   units in all}; {0, 0} when that call did not run the fused detector (see IA3_TUNE_SEED_SKIP) */
+int ia3_seed_skip_stats(double* out2);
 /* per-kernel timing with HIP events on the library stream (off by default) */
 int ia3_profile_enable(int on);
 int ia3_profile_collect(char* buf, int len); /* "kernel,count,total_ms\n" lines since last collect */
@@ -129,6 +132,14 @@ int ia3_profile_collect(char* buf, int len); /* "kernel,count,total_ms\n" lines 
  * the 3x3x3 candidate test on tiles held in LDS: the front-filtered stack is never stored; 0 = the plane-wise filter
  * writes it and the tiled detector reads it back.  Seeds are identical bit for bit. */
 #define IA3_TUNE_SEED_FUSED 15
+/* IA3_TUNE_SEED_SKIP: 1 = the fused detector of IA3_TUNE_SEED_FUSED leaves out the planes of a tile on which no
+ * voxel can pass the candidate test: the column kernel reports the largest value of the short filter's axis-0 result per
+ * plane, row and 32 columns, and a certified bound of max_im made from it (csrc/ia3_seedskip.h) is set against the
+ * threshold and the lower bound of min_im; 2 (default) = and, with a dynamic threshold, the first-stage candidate list is
+ * made at the first (highest) level instead of the lowest, with the seed stage started over at the lowest level when
+ * level 0 yields fewer than min_dynamic_seeds seeds; 0 = every plane of every tile is filtered and tested, list at the
+ * lowest level.  Seeds are identical bit for bit. */
+#define IA3_TUNE_SEED_SKIP 16
 /* IA3_DEBUG_FIT_MAXFEV: PROFILING ONLY, changes results: > 0 caps the function evaluations of every fit (MINPACK's maxfev),
  * which splits the fit kernel's time into its fixed and its per-evaluation part; 0 (default) = the reference's limits. */
 #define IA3_DEBUG_FIT_MAXFEV 100
