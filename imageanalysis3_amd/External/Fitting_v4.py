@@ -5,17 +5,73 @@ The class keeps the reference's constructor, ``firstfit()`` / ``repeatfit()`` an
 callers read (``ps``, ``centers_fit``, ``success``, ``n_iter``, ``centers``).  The float64 residual
 stack ``im_subtr`` / ``im_add`` and the per-seed ``ims_rec`` arrays of the reference are internal
 state of its Gauss-Seidel loop; the device path never materialises them (fit.hip header).
+
+The module's 2-D FFT aligners are here as well (:733-820, :422-424): ``blurnorm2d`` (the box blur is
+*subtracted* here, divided in ``alignment_tools``), ``fftalign_2d`` / ``fft3d_from2d`` with this module's
+offset convention (``[y, x] - im2.shape + 1``), its defaults and ``return_cor``, all on the device through
+the entries ``alignment_tools`` uses (fft_align.hip), and the small host helpers ``minmax``, ``translate``
+and ``closest_faster``.  ``plt_val=True`` (matplotlib figures) is not provided.
 """
 import ctypes as C
 import numpy as np
 
 from .. import _lib as L
+from .. import alignment_tools as _at
 
 
 def in_dim(x, y, z, xmax, ymax, zmax):
     """External/Fitting_v4.py:399-401."""
     keep = ((x >= 0) & (x < xmax) & (y >= 0) & (y < ymax) & (z >= 0) & (z < zmax)) > 0
     return x[keep], y[keep], z[keep]
+
+
+def closest_faster(xyz, ic, tree, rsearch=6):
+    """External/Fitting_v4.py:422-424 — the columns (3, m) of the rows of ``xyz`` whose nearest point of ``tree`` (the
+    caller's ``scipy.spatial.cKDTree``, searched up to ``rsearch``) is point number ``ic``."""
+    _, nearest = tree.query(xyz, distance_upper_bound=rsearch)
+    return xyz[nearest == ic].T
+
+
+def blurnorm2d(im, gb):
+    """External/Fitting_v4.py:733-737 — the image minus its ``gb x gb`` box blur (float32), on the device."""
+    return _at._blurnorm2d(im, gb, L.BLUR_SUBTRACT)
+
+
+def fft3d_from2d(im1, im2, gb=5, max_disp=150, plt_val=False, return_cor=False):
+    """External/Fitting_v4.py:738-752 — integer [tz, tx, ty] from the blur-subtracted z- and then y-max-projections
+    (with the two correlation values if ``return_cor``); ndarrays or DeviceStacks, everything on the device."""
+    if plt_val:
+        raise NotImplementedError("plt_val=True (matplotlib figures) is not provided")
+    return _at._fft3d_from2d(im1, im2, gb, L.BLUR_SUBTRACT, L.OFFSET_FITTING_V4, max_disp, return_cor)
+
+
+def fftalign_2d(im1, im2, center=[0, 0], max_disp=50, plt_val=False, return_cor=False):
+    """External/Fitting_v4.py:754-807 — (xt, yt) of the windowed peak of the normalised cross-correlation, counted from
+    ``im2``'s far corner (``[y, x] - im2.shape + 1``); with ``return_cor`` also the peak over the smaller image's size."""
+    if plt_val:
+        raise NotImplementedError("plt_val=True (matplotlib figures) is not provided")
+    return _at._fftalign_2d(im1, im2, center, max_disp, L.OFFSET_FITTING_V4, return_cor)
+
+
+def minmax(im, min_=None, max_=None):
+    """External/Fitting_v4.py:808-811 — float32 image rescaled so that [min_, max_] (default: its own range) is [0, 1]."""
+    lo = np.min(im) if min_ is None else min_
+    hi = np.max(im) if max_ is None else max_
+    return (np.array(im, dtype=np.float32) - lo) / (hi - lo)
+
+
+def translate(im, trans):
+    """External/Fitting_v4.py:812-820 — N-D image moved by the rounded ``-trans`` (``out[i] = im[i + t]``); what moves
+    in from outside is the image's median (an integer image comes back as float64, as ``zeros + median`` does)."""
+    im = np.asarray(im)
+    t = np.array(np.round(trans), dtype=int)
+    fill = np.median(im)
+    out = np.empty(im.shape, dtype=(np.zeros(1, dtype=im.dtype) + fill).dtype)
+    out[...] = fill
+    src = tuple(slice(max(k, 0), min(n, n + k)) for k, n in zip(t, im.shape))
+    dst = tuple(slice(max(-k, 0), min(n, n - k)) for k, n in zip(t, im.shape))
+    out[dst] = im[src]
+    return out
 
 
 def gaussfit_batch(ims, Xs, centers, delta_center=3., min_w=0.5, max_w=4., init_w=1.5):

@@ -13,6 +13,8 @@ LIB_PATH = os.environ.get("IA3_LIB_PATH") or os.path.join(_HERE, "libia3.so")   
 IA3_U16, IA3_F32 = 0, 1
 IA3_OK, IA3_EINVAL, IA3_EHIP, IA3_ENOMEM, IA3_ECAPACITY, IA3_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 MODE_REFLECT, MODE_NEAREST, MODE_CONSTANT = 0, 1, 2
+BLUR_DIVIDE, BLUR_SUBTRACT = 0, 1                   # ia3_blurnorm2d modes
+OFFSET_ALIGNMENT_TOOLS, OFFSET_FITTING_V4 = 0, 1    # fftalign_2d offset conventions
 
 EXPORTS = [
     "ia3_init", "ia3_last_error", "ia3_version", "ia3_device_name", "ia3_sync", "ia3_stream",
@@ -30,6 +32,7 @@ EXPORTS = [
     "ia3_fit_destroy", "ia3_fit_seeds", "ia3_fit_fov_dev", "ia3_fit_fov_stats", "ia3_fit_fov_wait_share", "ia3_fit_fovs",
     "ia3_gaussfit_voxels",
     "ia3_fftalign_2d", "ia3_fft3d_from2d", "ia3_fft3d_from2d_dev", "ia3_phase_xcorr3d", "ia3_phase_xcorr3d_dev",
+    "ia3_blurnorm2d", "ia3_fftalign_2d_ex", "ia3_fft3d_from2d_ex", "ia3_fft3d_from2d_dev_ex",
     "ia3_stack_crop", "ia3_warp3d", "ia3_warp3d_dev",
     "ia3_align_image_dev", "ia3_process_movies", "ia3_drift_ref_create", "ia3_drift_ref_free", "ia3_align_image_ref",
 ]

@@ -1,17 +1,41 @@
 """Drop-in for the hot-path part of the reference's ``alignment_tools.py`` (:278-353):
-pixel-level drift from max-projections by FFT cross-correlation, on the device (fft_align.hip)."""
+pixel-level drift from max-projections by FFT cross-correlation, on the device (fft_align.hip).
+The underscored helpers carry the mode / offset-convention switches that ``External.Fitting_v4``'s
+twins of these functions use."""
 import ctypes as C
 import numpy as np
 
 from . import _lib as L
 
 
+def _blurnorm2d(im, gb, mode):
+    """OpenCV's normalised ``gb x gb`` box blur of ``im.astype(np.float32)`` and the divide (``BLUR_DIVIDE``) or subtract (``BLUR_SUBTRACT``) that
+    follows it, by the box kernel of fft_align.hip (ia3_blurnorm2d: anchor ``gb // 2``, BORDER_REFLECT_101)."""
+    a = np.ascontiguousarray(im, dtype=np.float32)
+    if a.ndim != 2:
+        raise IndexError("blurnorm2d takes a 2-D image")
+    out = np.empty_like(a)
+    L.check(L.lib().ia3_blurnorm2d(L.ptr(a), a.shape[0], a.shape[1], int(gb), int(mode), L.ptr(out)))
+    return out
+
+
 def blurnorm2d(im, gb):
-    """alignment_tools.py:278-283 needs ``cv2.blur``; OpenCV is an optional dependency of the reference
-    used only when ``gb > 1`` (off the default path, ``fft_filt_size=0`` at correction_tools/alignment.py:141)."""
-    import cv2  # noqa: F401  (raises ImportError where the reference would)
-    im_ = im.astype(np.float32)
-    return im_ / cv2.blur(im_, (gb, gb))
+    """alignment_tools.py:278-283 — the image divided by its ``gb x gb`` box blur (float32), on the device."""
+    return _blurnorm2d(im, gb, L.BLUR_DIVIDE)
+
+
+def _fftalign_2d(im1, im2, center, max_disp, convention, return_cor):
+    a = np.ascontiguousarray(im1, dtype=np.float64)
+    b = np.ascontiguousarray(im2, dtype=np.float64)
+    if a.ndim != 2 or b.ndim != 2:
+        raise IndexError("fftalign_2d takes 2-D images")
+    c = np.ascontiguousarray(center, dtype=np.float64)
+    out = (C.c_int * 2)()
+    cor = C.c_double(0.)
+    L.check(L.lib().ia3_fftalign_2d_ex(L.dptr(a), a.shape[0], a.shape[1], L.dptr(b), b.shape[0], b.shape[1],
+                                       L.dptr(c), C.c_double(float(max_disp)), int(convention), out,
+                                       C.byref(cor) if return_cor else None))
+    return (int(out[0]), int(out[1]), float(cor.value)) if return_cor else (int(out[0]), int(out[1]))
 
 
 def fftalign_2d(im1, im2, center=[0, 0], max_disp=150, plt_val=False):
@@ -27,20 +51,30 @@ def fftalign_2d(im1, im2, center=[0, 0], max_disp=150, plt_val=False):
     return int(out[0]), int(out[1])
 
 
+def _fft3d_from2d(im1, im2, gb, mode, convention, max_disp, return_cor):
+    """The max-projection chain on the device (ia3_fft3d_from2d(_dev)_ex): projections, their box-blur normalisation
+    when ``gb > 1`` and the correlations; ndarrays are uploaded, resident stacks are used where they are."""
+    out = (C.c_int * 3)()
+    cor = (C.c_double * 2)()
+    pc = cor if return_cor else None
+    if isinstance(im1, L.DeviceStack) and isinstance(im2, L.DeviceStack):
+        L.check(L.lib().ia3_fft3d_from2d_dev_ex(im1._h, im2._h, int(gb), int(mode), int(convention),
+                                                C.c_double(float(max_disp)), out, pc))
+    else:
+        a, b = L.as_stack_array(_host(im1)), L.as_stack_array(_host(im2))
+        if a.shape != b.shape or a.dtype != b.dtype:
+            raise IndexError("fft3d_from2d needs two stacks of the same shape and dtype")
+        L.check(L.lib().ia3_fft3d_from2d_ex(L.ptr(a), L.ptr(b), L.dtype_code(a), a.shape[0], a.shape[1], a.shape[2],
+                                            int(gb), int(mode), int(convention), C.c_double(float(max_disp)), out, pc))
+    t = np.array([out[0], out[1], out[2]])
+    return (t, float(cor[0]), float(cor[1])) if return_cor else t
+
+
 def fft3d_from2d(im1, im2, gb=5, max_disp=150):
-    """alignment_tools.py:330-353 — integer [tz, tx, ty]; max-projections and FFTs on the device.
-    ``im1``/``im2`` may be ndarrays or DeviceStacks."""
+    """alignment_tools.py:330-353 — integer [tz, tx, ty]; max-projections, their blur normalisation (``gb > 1``) and the
+    FFTs on the device.  ``im1``/``im2`` may be ndarrays or DeviceStacks; a resident pair is never downloaded."""
     if gb > 1:
-        # cv2-normalised variant: projections on the host exactly as the reference, FFT on the device
-        i1, i2 = _host(im1), _host(im2)
-        im1_ = blurnorm2d(np.max(i1, 0), gb)
-        im2_ = blurnorm2d(np.max(i2, 0), gb)
-        tx, ty = fftalign_2d(im1_, im2_, center=[0, 0], max_disp=max_disp)
-        sx, sy = im1_.shape
-        im1_t = blurnorm2d(np.max(i1[:, max(tx, 0):sx + tx, max(ty, 0):sy + ty], axis=-1), gb)
-        im2_t = blurnorm2d(np.max(i2[:, max(-tx, 0):sx - tx, max(-ty, 0):sy - ty], axis=-1), gb)
-        tz, _ = fftalign_2d(im1_t, im2_t, center=[0, 0], max_disp=max_disp)
-        return np.array([tz, tx, ty])
+        return _fft3d_from2d(im1, im2, gb, L.BLUR_DIVIDE, L.OFFSET_ALIGNMENT_TOOLS, max_disp, False)
     out = (C.c_int * 3)()
     if isinstance(im1, L.DeviceStack) and isinstance(im2, L.DeviceStack):
         L.check(L.lib().ia3_fft3d_from2d_dev(im1._h, im2._h, C.c_double(float(max_disp)), out))

@@ -187,9 +187,73 @@ __global__ __launch_bounds__(1024) void window_argmax_k(const double* __restrict
   if (threadIdx.x == 0) { *out_idx = si[0]; *out_val = sv[0]; }
 }
 
-// fftalign_2d on device-resident 2-D float64 images (alignment_tools.py:286-328)
+// ---- box-blur normalisation (alignment_tools.py:278-283 divides, External/Fitting_v4.py:733-737 subtracts) ----------
+// cv2.blur(im.astype(float32), (gb, gb)) of a 2-D image followed by im / blurred (mode 0) or im - blurred (mode 1):
+// normalised gb x gb box, anchor gb / 2 in both axes (the window of output (i, j) starts at i - gb / 2, j - gb / 2, so an
+// even gb is asymmetric), border BORDER_REFLECT_101 (-1 -> 1, n -> n - 2; periodic with 2 (n - 1), a length-1 axis is all
+// index 0).  Every window is summed in float64, each of its rows left to right and then the row sums top to bottom, the
+// sum is multiplied by the double 1 / gb^2 and rounded to float32; the divide / subtract is float32.  Exact in any order
+// for integer-valued images (every uint16 stack).  OpenCV is not available to this project: the arithmetic follows its
+// generic CV_32F path as published and is pinned against a NumPy restatement only.
+//
+// One block = a 16 x 64 tile of outputs; the tile plus its gb - 1 halo rows / columns goes into LDS as float32 through
+// the reflected index, so every load is inside the image (also for the outputs of a ragged tile that are never stored)
+// and there is no border branch.  Rows of 64 + gb - 1 floats: an odd or even stride, but a wave reads 64 consecutive
+// floats of one row at a time, which is conflict free at any stride.
+constexpr int BLUR_MAX_GB = IA3_BLUR_MAX_GB, BLUR_TX = 64, BLUR_TY = 16;
+__device__ __forceinline__ int reflect101(int i, int n) {
+  if (n == 1) return 0;
+  const int p = 2 * (n - 1);
+  int m = i % p;
+  m = m < 0 ? m + p : m;
+  return m < n ? m : p - m;
+}
+template <class TI, class TO>
+__global__ __launch_bounds__(256) void blurnorm_k(const TI* __restrict__ im, int sx, int sy, int gb, int mode,
+                                                  TO* __restrict__ out) {
+  __shared__ float tile[(BLUR_TY + BLUR_MAX_GB - 1) * (BLUR_TX + BLUR_MAX_GB - 1)];
+  const int a = gb / 2, tw = BLUR_TX + gb - 1, th = BLUR_TY + gb - 1;
+  const int i0 = blockIdx.y * BLUR_TY, j0 = blockIdx.x * BLUR_TX;
+  for (int e = threadIdx.x; e < th * tw; e += 256) {
+    const int r = e / tw, c = e - r * tw;
+    tile[e] = (float)im[(size_t)reflect101(i0 - a + r, sx) * sy + reflect101(j0 - a + c, sy)];
+  }
+  __syncthreads();
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const double scale = 1.0 / (double)(gb * gb);
+  for (int q = 0; q < BLUR_TY / 4; ++q) {
+    const int r = ty + 4 * q;
+    double sum = 0.0;
+    for (int u = 0; u < gb; ++u) {
+      const float* row = tile + (r + u) * tw + tx;
+      double rs = 0.0;
+      for (int v = 0; v < gb; ++v) rs += (double)row[v];
+      sum += rs;
+    }
+    const float blurred = (float)(sum * scale);
+    const float v0 = tile[(r + a) * tw + tx + a];
+    if (i0 + r < sx && j0 + tx < sy) out[(size_t)(i0 + r) * sy + j0 + tx] = (TO)(mode ? v0 - blurred : v0 / blurred);
+  }
+}
+int blur_check(int gb, int mode) {
+  if (gb < 1 || gb > BLUR_MAX_GB) return set_error(IA3_EINVAL, "box size gb=%d outside the supported range 1..%d", gb, BLUR_MAX_GB);
+  if (mode != 0 && mode != 1) return set_error(IA3_EINVAL, "blur mode %d: 0 (divide) or 1 (subtract)", mode);
+  if (mode == 1 && gb <= 1) return set_error(IA3_EINVAL, "subtracting a gb=%d blur leaves a zero image (0/0 in the correlation)", gb);
+  return IA3_OK;
+}
+template <class TI, class TO>
+void launch_blurnorm(const TI* im, int sx, int sy, int gb, int mode, TO* out, hipStream_t st) {
+  ProfScope ps("blurnorm2d");
+  dim3 g((sy + BLUR_TX - 1) / BLUR_TX, (sx + BLUR_TY - 1) / BLUR_TY);
+  hipLaunchKernelGGL((blurnorm_k<TI, TO>), g, dim3(256), 0, st, im, sx, sy, gb, mode, out);
+}
+
+
+// fftalign_2d on device-resident 2-D float64 images (alignment_tools.py:286-328).  convention 0: the offset of alignment_tools,
+// -floor(cor.shape / 2) + [y, x]; 1: External/Fitting_v4.py:781, [y, x] - im2.shape + 1 (the same for equal shapes).
+// out_cor (may be null): the windowed peak / prod(min(im1.shape, im2.shape)) (Fitting_v4.py:806).
 int fftalign2d_dev(const double* im1, int s1x, int s1y, const double* im2, int s2x, int s2y,
-                   const double center[2], double max_disp, int out[2]) {
+                   const double center[2], double max_disp, int out[2], int convention = 0, double* out_cor = nullptr) {
   hipStream_t st = stream();
   if (s1x < 1 || s1y < 1 || s2x < 1 || s2y < 1) return set_error(IA3_EINVAL, "empty image in fftalign_2d");
   const int cx = s1x + s2x - 1, cy = s1y + s2y - 1;
@@ -221,12 +285,19 @@ int fftalign2d_dev(const double* im1, int s1x, int s1y, const double* im2, int s
   hipLaunchKernelGGL(window_argmax_k, dim3(1), dim3(1024), 0, st, (const double*)a.as<double>(), cx, cy, Fy,
                      1.0 / (double)nreal, x_min, x_max, y_min, y_max, d_idx, d_val);
   IA3_KCHECK();
-  long long idx = 0;
-  IA3_HIP(hipMemcpyAsync(&idx, d_idx, sizeof(idx), hipMemcpyDeviceToHost, st));
+  struct { long long idx; double val; } peak = {0, 0.0};
+  IA3_HIP(hipMemcpyAsync(&peak, d_idx, sizeof(peak), hipMemcpyDeviceToHost, st));
   IA3_HIP(hipStreamSynchronize(st));
+  const long long idx = peak.idx;
   const int yy = (int)(idx / cy), xx = (int)(idx % cy);
-  out[0] = -(cx / 2) + yy;   // -floor(shape/2) + [y, x]   (:327)
-  out[1] = -(cy / 2) + xx;
+  if (convention == 0) {
+    out[0] = -(cx / 2) + yy;   // -floor(shape/2) + [y, x]   (:327)
+    out[1] = -(cy / 2) + xx;
+  } else {
+    out[0] = yy - s2x + 1;     // [y, x] - im2.shape + 1     (Fitting_v4.py:781)
+    out[1] = xx - s2y + 1;
+  }
+  if (out_cor) *out_cor = peak.val / ((double)(s1x < s2x ? s1x : s2x) * (double)(s1y < s2y ? s1y : s2y));
   return IA3_OK;
 }
 
@@ -666,24 +737,36 @@ int ia3_fftalign_2d(const double* im1, int s1x, int s1y, const double* im2, int 
   return fftalign2d_dev(a.as<double>(), s1x, s1y, b.as<double>(), s2x, s2y, center, max_disp, out_xy);
 }
 
-// alignment_tools.py:330-353 with gb <= 1 (the production default fft_filt_size=0, alignment.py:141,191-193)
-int ia3_fft3d_from2d_dev(const ia3_stack* im1, const ia3_stack* im2, double max_disp, int* out_zxy) {
+// alignment_tools.py:330-353 (mode 0; gb <= 1: no blur, the production default fft_filt_size=0, alignment.py:141,191-193)
+// and External/Fitting_v4.py:738-752 (mode 1, convention 1) on resident stacks.  With gb > 1 each max-projection is
+// cast to float32, box-blur normalised and widened again on the device before it is correlated.
+static int fft3d_from2d_chain(const ia3_stack* im1, const ia3_stack* im2, int gb, int mode, int convention, double max_disp,
+                              int* out_zxy, double* out_cor2) {
   int rc = ensure_init(); if (rc) return rc;
   if (!im1 || !im2 || !out_zxy) return set_error(IA3_EINVAL, "null argument");
   if (im1->dtype != im2->dtype) return set_error(IA3_EINVAL, "stacks differ in dtype");
+  if (convention != 0 && convention != 1) return set_error(IA3_EINVAL, "offset convention %d: 0 (alignment_tools) or 1 (Fitting_v4)", convention);
+  const bool blur = gb > 1 || mode != 0;
+  if (blur) { rc = blur_check(gb, mode); if (rc) return rc; }
   hipStream_t st = stream();
   const int sx = im1->X, sy = im1->Y;
   const double center[2] = {0, 0};
   int txy[2], tzq[2];
   {
-    Scratch p1((size_t)im1->X * im1->Y * sizeof(double)), p2((size_t)im2->X * im2->Y * sizeof(double));
-    if (!p1.p || !p2.p) return IA3_ENOMEM;
+    const size_t n1 = (size_t)im1->X * im1->Y, n2 = (size_t)im2->X * im2->Y;
+    Scratch p1(n1 * sizeof(double)), p2(n2 * sizeof(double)), b1(blur ? n1 * sizeof(double) : 8), b2(blur ? n2 * sizeof(double) : 8);
+    if (!p1.p || !p2.p || !b1.p || !b2.p) return IA3_ENOMEM;
     {
       ProfScope ps("maxproj_z");
       if (im1->dtype == IA3_F32) { launch_maxproj_z<float>(im1, 0, im1->X, 0, im1->Y, p1.as<double>(), st); launch_maxproj_z<float>(im2, 0, im2->X, 0, im2->Y, p2.as<double>(), st); }
       else { launch_maxproj_z<uint16_t>(im1, 0, im1->X, 0, im1->Y, p1.as<double>(), st); launch_maxproj_z<uint16_t>(im2, 0, im2->X, 0, im2->Y, p2.as<double>(), st); }
     }
-    rc = fftalign2d_dev(p1.as<double>(), im1->X, im1->Y, p2.as<double>(), im2->X, im2->Y, center, max_disp, txy);
+    if (blur) {
+      launch_blurnorm((const double*)p1.as<double>(), im1->X, im1->Y, gb, mode, b1.as<double>(), st);
+      launch_blurnorm((const double*)p2.as<double>(), im2->X, im2->Y, gb, mode, b2.as<double>(), st);
+    }
+    rc = fftalign2d_dev(blur ? b1.as<double>() : p1.as<double>(), im1->X, im1->Y, blur ? b2.as<double>() : p2.as<double>(), im2->X, im2->Y,
+                        center, max_disp, txy, convention, out_cor2);
     if (rc) return rc;
   }
   const int tx = txy[0], ty = txy[1];
@@ -694,18 +777,32 @@ int ia3_fft3d_from2d_dev(const ia3_stack* im1, const ia3_stack* im2, double max_
   const int n1x = a1 - a0, n1y = b1 - b0, n2x = c1 - c0, n2y = d1 - d0;
   if (n1x < 1 || n1y < 1 || n2x < 1 || n2y < 1) return set_error(IA3_EINVAL, "xy shift (%d,%d) leaves no overlap", tx, ty);
   {
-    Scratch q1((size_t)im1->Z * n1x * sizeof(double)), q2((size_t)im2->Z * n2x * sizeof(double));
-    if (!q1.p || !q2.p) return IA3_ENOMEM;
+    const size_t n1 = (size_t)im1->Z * n1x, n2 = (size_t)im2->Z * n2x;
+    Scratch q1(n1 * sizeof(double)), q2(n2 * sizeof(double)), e1(blur ? n1 * sizeof(double) : 8), e2(blur ? n2 * sizeof(double) : 8);
+    if (!q1.p || !q2.p || !e1.p || !e2.p) return IA3_ENOMEM;
     {
       ProfScope ps("maxproj_y");
       if (im1->dtype == IA3_F32) { launch_maxproj_y<float>(im1, a0, n1x, b0, n1y, q1.as<double>(), st); launch_maxproj_y<float>(im2, c0, n2x, d0, n2y, q2.as<double>(), st); }
       else { launch_maxproj_y<uint16_t>(im1, a0, n1x, b0, n1y, q1.as<double>(), st); launch_maxproj_y<uint16_t>(im2, c0, n2x, d0, n2y, q2.as<double>(), st); }
     }
-    rc = fftalign2d_dev(q1.as<double>(), im1->Z, n1x, q2.as<double>(), im2->Z, n2x, center, max_disp, tzq);
+    if (blur) {
+      launch_blurnorm((const double*)q1.as<double>(), im1->Z, n1x, gb, mode, e1.as<double>(), st);
+      launch_blurnorm((const double*)q2.as<double>(), im2->Z, n2x, gb, mode, e2.as<double>(), st);
+    }
+    rc = fftalign2d_dev(blur ? e1.as<double>() : q1.as<double>(), im1->Z, n1x, blur ? e2.as<double>() : q2.as<double>(), im2->Z, n2x,
+                        center, max_disp, tzq, convention, out_cor2 ? out_cor2 + 1 : nullptr);
     if (rc) return rc;
   }
   out_zxy[0] = tzq[0]; out_zxy[1] = tx; out_zxy[2] = ty;
   return IA3_OK;
+}
+
+int ia3_fft3d_from2d_dev(const ia3_stack* im1, const ia3_stack* im2, double max_disp, int* out_zxy) {
+  return fft3d_from2d_chain(im1, im2, 0, 0, 0, max_disp, out_zxy, nullptr);
+}
+int ia3_fft3d_from2d_dev_ex(const ia3_stack* im1, const ia3_stack* im2, int gb, int mode, int convention, double max_disp,
+                            int* out_zxy, double* out_cor2) {
+  return fft3d_from2d_chain(im1, im2, gb, mode, convention, max_disp, out_zxy, out_cor2);
 }
 
 int ia3_fft3d_from2d(const void* im1, const void* im2, int dtype, int Z, int X, int Y, double max_disp, int* out_zxy) {
@@ -715,6 +812,46 @@ int ia3_fft3d_from2d(const void* im1, const void* im2, int dtype, int Z, int X, 
   if (!rc) rc = ia3_fft3d_from2d_dev(a, b, max_disp, out_zxy);
   ia3_stack_free(a); ia3_stack_free(b);
   return rc;
+}
+int ia3_fft3d_from2d_ex(const void* im1, const void* im2, int dtype, int Z, int X, int Y, int gb, int mode, int convention,
+                        double max_disp, int* out_zxy, double* out_cor2) {
+  ia3_stack *a = nullptr, *b = nullptr;
+  int rc = ia3_stack_upload(im1, dtype, Z, X, Y, &a); if (rc) return rc;
+  rc = ia3_stack_upload(im2, dtype, Z, X, Y, &b);
+  if (!rc) rc = ia3_fft3d_from2d_dev_ex(a, b, gb, mode, convention, max_disp, out_zxy, out_cor2);
+  ia3_stack_free(a); ia3_stack_free(b);
+  return rc;
+}
+
+int ia3_fftalign_2d_ex(const double* im1, int s1x, int s1y, const double* im2, int s2x, int s2y, const double* center,
+                       double max_disp, int convention, int* out_xy, double* out_cor) {
+  int rc = ensure_init(); if (rc) return rc;
+  if (!im1 || !im2 || !center || !out_xy) return set_error(IA3_EINVAL, "null argument");
+  if (s1x < 1 || s1y < 1 || s2x < 1 || s2y < 1) return set_error(IA3_EINVAL, "empty image in fftalign_2d");
+  if (convention != 0 && convention != 1) return set_error(IA3_EINVAL, "offset convention %d: 0 (alignment_tools) or 1 (Fitting_v4)", convention);
+  hipStream_t st = stream();
+  Scratch a((size_t)s1x * s1y * sizeof(double)), b((size_t)s2x * s2y * sizeof(double));
+  if (!a.p || !b.p) return IA3_ENOMEM;
+  IA3_HIP(hipMemcpyAsync(a.p, im1, (size_t)s1x * s1y * sizeof(double), hipMemcpyHostToDevice, st));
+  IA3_HIP(hipMemcpyAsync(b.p, im2, (size_t)s2x * s2y * sizeof(double), hipMemcpyHostToDevice, st));
+  return fftalign2d_dev(a.as<double>(), s1x, s1y, b.as<double>(), s2x, s2y, center, max_disp, out_xy, convention, out_cor);
+}
+
+int ia3_blurnorm2d(const float* im, int sx, int sy, int gb, int mode, float* out) {
+  int rc = ensure_init(); if (rc) return rc;
+  if (!im || !out) return set_error(IA3_EINVAL, "null argument");
+  if (sx < 1 || sy < 1) return set_error(IA3_EINVAL, "empty image in blurnorm2d");
+  rc = blur_check(gb, mode); if (rc) return rc;
+  hipStream_t st = stream();
+  const size_t bytes = (size_t)sx * sy * sizeof(float);
+  Scratch a(bytes), b(bytes);
+  if (!a.p || !b.p) return IA3_ENOMEM;
+  IA3_HIP(hipMemcpyAsync(a.p, im, bytes, hipMemcpyHostToDevice, st));
+  launch_blurnorm((const float*)a.as<float>(), sx, sy, gb, mode, b.as<float>(), st);
+  IA3_KCHECK();
+  IA3_HIP(hipMemcpyAsync(out, b.p, bytes, hipMemcpyDeviceToHost, st));
+  IA3_HIP(hipStreamSynchronize(st));
+  return IA3_OK;
 }
 
 // phase_cross_correlation(reference, moving, upsample_factor, normalization) -> shift, error, phasediff

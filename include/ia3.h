@@ -380,6 +380,35 @@ int ia3_fftalign_2d(const double* im1, int s1x, int s1y, const double* im2, int 
 int ia3_fft3d_from2d(const void* im1, const void* im2, int dtype, int Z, int X, int Y, double max_disp,
                      int* out_zxy);
 int ia3_fft3d_from2d_dev(const ia3_stack* im1, const ia3_stack* im2, double max_disp, int* out_zxy);
+/* Box-blur normalisation of a 2-D float32 image (sx x sy, host in, host out): cv2.blur(im, (gb, gb)) followed by
+ * im / blurred (mode IA3_BLUR_DIVIDE, alignment_tools.py:278-283) or im - blurred (mode IA3_BLUR_SUBTRACT,
+ * External/Fitting_v4.py:733-737).  Normalised gb x gb box, anchor gb / 2 in both axes (even gb is asymmetric), border
+ * BORDER_REFLECT_101; each window summed in float64 (rows first), times the double 1 / gb^2, rounded to float32, then
+ * the float32 divide / subtract.  Supported: 1 <= gb <= IA3_BLUR_MAX_GB; mode 1 needs gb >= 2 (gb = 1 subtracts the
+ * image from itself); anything else is IA3_EINVAL.  OpenCV is not available to this project: the arithmetic follows its
+ * published generic CV_32F path and is pinned against a NumPy restatement of the rules above only.  Exact in any
+ * summation order for integer-valued images; for other float32 data OpenCV's running column sums may differ in the last
+ * bit. */
+#define IA3_BLUR_MAX_GB 32
+#define IA3_BLUR_DIVIDE 0
+#define IA3_BLUR_SUBTRACT 1
+int ia3_blurnorm2d(const float* im, int sx, int sy, int gb, int mode, float* out);
+/* fftalign_2d with the choice of offset convention and the correlation value.  convention IA3_OFFSET_ALIGNMENT_TOOLS:
+ * -floor(cor.shape / 2) + [y, x] (what ia3_fftalign_2d returns); IA3_OFFSET_FITTING_V4: [y, x] - im2.shape + 1
+ * (External/Fitting_v4.py:781) — the two agree only for images of one shape.  out_cor (may be NULL): the windowed peak
+ * / prod(min(im1.shape, im2.shape)) (Fitting_v4.py:806). */
+#define IA3_OFFSET_ALIGNMENT_TOOLS 0
+#define IA3_OFFSET_FITTING_V4 1
+int ia3_fftalign_2d_ex(const double* im1, int s1x, int s1y, const double* im2, int s2x, int s2y,
+                       const double* center, double max_disp, int convention, int* out_xy, double* out_cor);
+/* fft3d_from2d with the blur-normalised projections of gb > 1, all on the device: each max-projection is cast to float32,
+ * normalised as by ia3_blurnorm2d (gb, mode) and correlated as by ia3_fftalign_2d_ex (convention).  mode 0 with gb <= 1
+ * is the unblurred chain of ia3_fft3d_from2d; mode 1 (External/Fitting_v4.py:738-752) needs gb >= 2.  out_cor2 (may be
+ * NULL): the correlation values of the xy and of the z stage. */
+int ia3_fft3d_from2d_ex(const void* im1, const void* im2, int dtype, int Z, int X, int Y, int gb, int mode,
+                        int convention, double max_disp, int* out_zxy, double* out_cor2);
+int ia3_fft3d_from2d_dev_ex(const ia3_stack* im1, const ia3_stack* im2, int gb, int mode, int convention,
+                            double max_disp, int* out_zxy, double* out_cor2);
 /* skimage.registration.phase_cross_correlation(reference, moving, upsample_factor) as called at
  * correction_tools/alignment.py:491-494,631-632 and classes/preprocess.py:831-835 (published algorithm; pinned
  * against scikit-image 0.18.3 for normalization None, tests/golden/phase.npz).  normalization: 1 = "phase", 0 = None.  shift[3] = (dz, dx, dy) to apply to `moving`. */
