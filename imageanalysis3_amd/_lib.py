@@ -35,6 +35,8 @@ EXPORTS = [
     "ia3_blurnorm2d", "ia3_fftalign_2d_ex", "ia3_fft3d_from2d_ex", "ia3_fft3d_from2d_dev_ex",
     "ia3_stack_crop", "ia3_warp3d", "ia3_warp3d_dev",
     "ia3_align_image_dev", "ia3_process_movies", "ia3_drift_ref_create", "ia3_drift_ref_free", "ia3_align_image_ref",
+    "ia3_stack_order_stats_dev", "ia3_stack_percentiles_dev", "ia3_clip_sum_z_dev",
+    "ia3_gaussian_filter2d_f64_dev", "ia3_gaussian_filter2d_f64", "ia3_illumination_image_profile_dev",
 ]
 
 
@@ -241,6 +243,21 @@ class DeviceStack(object):
         check(lib().ia3_stack_download(self._h, ptr(out)))
         return out
 
+    def order_stats(self, ranks):
+        """``np.sort(stack, axis=None)[ranks]`` (at most 16 ranks) selected on the device: array of the stack dtype."""
+        r = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
+        out = np.empty(len(r), dtype=self.dtype)
+        check(lib().ia3_stack_order_stats_dev(self._h, r.ctypes.data_as(C.POINTER(C.c_longlong)), len(r), ptr(out)))
+        return out
+
+    def percentiles(self, pers):
+        """``[scipy.stats.scoreatpercentile(stack, p) for p in pers]`` (at most 8) from exact order statistics selected
+        on the device: float64 array."""
+        p = np.ascontiguousarray(pers, dtype=np.float64).ravel()
+        out = np.empty(len(p), dtype=np.float64)
+        check(lib().ia3_stack_percentiles_dev(self._h, dptr(p), len(p), dptr(out)))
+        return out
+
     def free(self):
         if self._h is not None:
             lib().ia3_stack_free(self._h)
@@ -258,6 +275,84 @@ class DeviceStack(object):
 
     def __exit__(self, *a):
         self.free()
+
+
+class DeviceImage64(object):
+    """A float64 (X, Y) image resident in HBM (what ``ia3_clip_sum_z_dev`` writes and ``ia3_gaussian_filter2d_f64_dev``
+    reads and writes), kept in a library allocation of the same size."""
+
+    def __init__(self, shape, _store=None):
+        self.shape = (int(shape[0]), int(shape[1]))
+        # X * Y * 8 bytes, as a (2, X, Y) float32 stack of the library
+        self._store = DeviceStack.empty((2,) + self.shape, np.float32) if _store is None else _store
+        d = C.c_void_p()
+        check(lib().ia3_stack_info(self._store._h, None, None, None, None, C.byref(d)))
+        self.devptr = C.c_void_p(d.value)
+
+    @classmethod
+    def upload(cls, im):
+        a = np.ascontiguousarray(im, dtype=np.float64)
+        if a.ndim != 2:
+            raise IndexError("a 2-D image is required, got ndim=%d" % a.ndim)
+        raw = np.frombuffer(a.tobytes(), dtype=np.float32).reshape((2,) + a.shape)
+        return cls(a.shape, _store=DeviceStack.upload(raw))
+
+    def download(self):
+        return np.frombuffer(self._store.download().tobytes(), dtype=np.float64).reshape(self.shape).copy()
+
+    def free(self):
+        self._store.free()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+def clip_sum_z(stack, limits=None):
+    """``np.sum(np.clip(float64(stack), lo, hi), axis=0)`` (no clip for ``limits=None``) of a resident stack, planes added
+    in z order: a resident ``DeviceImage64``."""
+    out = DeviceImage64(stack.shape[1:])
+    lo, hi = (0.0, 0.0) if limits is None else (float(limits[0]), float(limits[1]))
+    try:
+        check(lib().ia3_clip_sum_z_dev(stack._h, 0 if limits is None else 1, C.c_double(lo), C.c_double(hi), out.devptr))
+    except Exception:
+        out.free()
+        raise
+    return out
+
+
+def taps_argument(sigma, truncate=4.0, max_radius=1024):
+    """(weights pointer or None, radius, keep-alive) for the entries that take SciPy's taps from NumPy: the taps of
+    ``gaussian_taps``; None where the library refuses the filter anyway (no positive sigma, radius above its maximum)."""
+    sigma, truncate = float(sigma), float(truncate)
+    if not (sigma > 0 and truncate > 0) or truncate * sigma + 0.5 >= max_radius + 1:
+        return None, 0, None
+    w, r = gaussian_taps(sigma, truncate)
+    return dptr(w), int(r), w
+
+
+def gaussian_filter2d_f64(im, sigma, truncate=4.0, mode=MODE_REFLECT):
+    """``scipy.ndimage.gaussian_filter`` of a float64 2-D image in float64, bit for bit: an ndarray in gives an ndarray
+    (``ia3_gaussian_filter2d_f64``), a ``DeviceImage64`` a new ``DeviceImage64`` (``ia3_gaussian_filter2d_f64_dev``)."""
+    wp, r, _keep = taps_argument(sigma, truncate)
+    if isinstance(im, DeviceImage64):
+        out = DeviceImage64(im.shape)
+        try:
+            check(lib().ia3_gaussian_filter2d_f64_dev(im.devptr, im.shape[0], im.shape[1], C.c_double(float(sigma)),
+                                                      C.c_double(float(truncate)), int(mode), wp, r, out.devptr))
+        except Exception:
+            out.free()
+            raise
+        return out
+    a = np.ascontiguousarray(im, dtype=np.float64)
+    if a.ndim != 2:
+        raise IndexError("a 2-D image is required, got ndim=%d" % a.ndim)
+    out = np.empty_like(a)
+    check(lib().ia3_gaussian_filter2d_f64(dptr(a), a.shape[0], a.shape[1], C.c_double(float(sigma)),
+                                          C.c_double(float(truncate)), int(mode), wp, r, dptr(out)))
+    return out
 
 
 def profile_enable(on=True):

@@ -8,6 +8,7 @@
 // order-preserving uint32 key of the float32 value), batched over the Z planes plus the whole stack, for the
 // two middle ranks NumPy averages.
 #include "ia3_rt.h"
+#include "ia3_key.h"
 #include <math.h>
 #include <vector>
 
@@ -21,14 +22,8 @@ __device__ __forceinline__ uint16_t to_u16(double t) {   // numpy .astype(np.uin
 }
 template <class T> __device__ __forceinline__ float ldf(const T* p, size_t i) { return (float)p[i]; }
 
-__device__ __forceinline__ uint32_t fkey(float v) {      // order-preserving key
-  uint32_t u = __float_as_uint(v);
-  return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-__device__ __forceinline__ float fkey_inv(uint32_t k) {
-  uint32_t u = (k & 0x80000000u) ? (k & 0x7fffffffu) : ~k;
-  return __uint_as_float(u);
-}
+using ia3key::fkey;       // order-preserving key (ia3_key.h)
+using ia3key::fkey_inv;
 
 constexpr int RB = 2048;  // buckets per pass (11 bits; last pass uses 10)
 struct SelState {         // per problem (plane z or whole stack) and rank r

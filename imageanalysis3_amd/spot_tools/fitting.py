@@ -29,22 +29,30 @@ def get_seeds(im, max_num_seeds=None, th_seed=150,
     if th_seed_per >= 100 or th_seed_per <= 50:
         use_percentile = False
         print(f"th_seed_per should be a percentile > 50, invalid value given ({th_seed_per}), so not use percentile here.")
-    if sel_center is not None:                                               # :56-68
-        if len(sel_center) != len(np.shape(im)):
-            raise IndexError("num of dimensions should match for selected center and image given.")
-        _center = np.array(sel_center, dtype=int)
-        _llims = np.max([np.zeros(len(im.shape)), _center - seed_radius], axis=0)
-        _rlims = np.min([np.array(im.shape), _center + seed_radius], axis=0)
-        _lims = np.array(np.transpose(np.stack([_llims, _rlims])), dtype=int)
+    if sel_center is not None and len(sel_center) != len(np.shape(im)):      # :56-58
+        raise IndexError("num of dimensions should match for selected center and image given.")
+    if use_percentile:   # :75-76: the threshold is a pair of exact order statistics of the whole image, taken where the
+        #                  seeds are found: one upload, percentiles, crop and seeding on the resident stack
+        if verbose:
+            _start_time = time.time()
+            print("-- start seeding image with a percentile threshold", end='')
+        with L.DeviceStack.upload(im) as _stack:
+            _final = _get_seeds_dev(_stack, max_num_seeds=max_num_seeds, th_seed_per=th_seed_per, use_percentile=True,
+                                    sel_center=sel_center, seed_radius=seed_radius, gfilt_size=gfilt_size,
+                                    background_gfilt_size=background_gfilt_size, filt_size=filt_size,
+                                    min_edge_distance=min_edge_distance, use_dynamic_th=use_dynamic_th,
+                                    dynamic_niters=dynamic_niters, min_dynamic_seeds=min_dynamic_seeds,
+                                    remove_hot_pixel=remove_hot_pixel, hot_pixel_th=hot_pixel_th, return_h=return_h)
+        if verbose:
+            print(f", found {len(_final)} seeds in {time.time()-_start_time:.2f}s")
+        return _final
+    if sel_center is not None:                                               # :59-68
+        _lims, _local_edges = _center_crop_lims(np.shape(im), sel_center, seed_radius)
         _im = im[tuple(slice(_l, _r) for _l, _r in _lims)]
-        _local_edges = _llims
     else:
         _local_edges = np.zeros(len(np.shape(im)))
         _im = im
-    if use_percentile:                                                       # :75-76 (whole image)
-        _th_seed = _score_at_percentile(im, th_seed_per) - _score_at_percentile(im, (100 - th_seed_per) / 2)
-    else:
-        _th_seed = th_seed
+    _th_seed = th_seed
     if verbose:
         _start_time = time.time()
         print(f"-- start seeding image, th={_th_seed:.2f}", end='')
@@ -90,6 +98,24 @@ def _score_at_percentile(a, per):
         return np.add.reduce(np.partition(flat, i)[i:i + 1] * np.array(1), axis=0) / 1.0
     w = np.array([(i + 1 - idx), (idx - i)], float)
     return np.add.reduce(np.partition(flat, [i, i + 1])[i:i + 2] * w, axis=0) / w.sum()
+
+
+def stack_percentile_threshold(stack, th_seed_per):
+    """The percentile threshold of get_seeds (spot_tools/fitting.py:75-76) on a resident ``DeviceStack``:
+    ``scoreatpercentile(im, per) - scoreatpercentile(im, (100 - per) / 2)`` from exact order statistics selected on the
+    device (``ia3_stack_percentiles_dev``), a NumPy float64 as the host arithmetic gives."""
+    _pers = np.array([th_seed_per, (100 - th_seed_per) / 2], dtype=np.float64)
+    _vals = np.empty(2, dtype=np.float64)
+    L.check(L.lib().ia3_stack_percentiles_dev(stack._h, L.dptr(_pers), 2, L.dptr(_vals)))
+    return _vals[0] - _vals[1]
+
+
+def _center_crop_lims(shape, sel_center, seed_radius):
+    """[start, stop) limits (3,2) of the +-seed_radius box around ``sel_center`` and its lower corner (:59-64)."""
+    _center = np.array(sel_center, dtype=int)
+    _llims = np.max([np.zeros(len(shape)), _center - seed_radius], axis=0)
+    _rlims = np.min([np.array(shape), _center + seed_radius], axis=0)
+    return np.array(np.transpose(np.stack([_llims, _rlims])), dtype=int), _llims
 
 
 def remove_edge_points(im, T_seeds, distance=2):
@@ -214,19 +240,26 @@ def _get_seeds_dev(stack, host_im=None, max_num_seeds=None, th_seed=150, th_seed
                    sel_center=None, seed_radius=30, gfilt_size=0.75, background_gfilt_size=7.5, filt_size=3,
                    min_edge_distance=2, use_dynamic_th=True, dynamic_niters=10, min_dynamic_seeds=1,
                    remove_hot_pixel=True, hot_pixel_th=3, return_h=False, verbose=False):
-    """get_seeds on a stack that is already resident in HBM (no second upload)."""
-    if sel_center is not None or use_percentile:
-        if host_im is None:
-            host_im = stack.download()
-        return get_seeds(host_im, max_num_seeds=max_num_seeds, th_seed=th_seed, th_seed_per=th_seed_per,
-                         use_percentile=use_percentile, sel_center=sel_center, seed_radius=seed_radius,
-                         gfilt_size=gfilt_size, background_gfilt_size=background_gfilt_size,
-                         filt_size=filt_size, min_edge_distance=min_edge_distance,
-                         use_dynamic_th=use_dynamic_th, dynamic_niters=dynamic_niters,
-                         min_dynamic_seeds=min_dynamic_seeds, remove_hot_pixel=remove_hot_pixel,
-                         hot_pixel_th=hot_pixel_th, return_h=return_h, verbose=verbose)
+    """get_seeds on a stack that is already resident in HBM (no second upload, no download): the percentile threshold
+    comes from ``ia3_stack_percentiles_dev`` over the whole stack, the ``sel_center`` crop from ``ia3_stack_crop``.
+    ``host_im`` is accepted for older callers and not used."""
     if th_seed_per >= 100 or th_seed_per <= 50:
+        use_percentile = False
         print(f"th_seed_per should be a percentile > 50, invalid value given ({th_seed_per}), so not use percentile here.")
+    if use_percentile:                                                       # :75-76 (whole image)
+        th_seed = stack_percentile_threshold(stack, th_seed_per)
+    if sel_center is not None:                                               # :56-68
+        if len(sel_center) != len(stack.shape):
+            raise IndexError("num of dimensions should match for selected center and image given.")
+        _lims, _local_edges = _center_crop_lims(stack.shape, sel_center, seed_radius)
+        with stack.crop(_lims) as _sub:
+            _final = _get_seeds_dev(_sub, max_num_seeds=max_num_seeds, th_seed=th_seed, gfilt_size=gfilt_size,
+                                    background_gfilt_size=background_gfilt_size, filt_size=filt_size,
+                                    min_edge_distance=min_edge_distance, use_dynamic_th=use_dynamic_th,
+                                    dynamic_niters=dynamic_niters, min_dynamic_seeds=min_dynamic_seeds,
+                                    remove_hot_pixel=remove_hot_pixel, hot_pixel_th=hot_pixel_th, return_h=return_h)
+        _final[:, :3] += _local_edges[np.newaxis, :]
+        return _final
     _p, _keep = L.make_seed_params(th_seed, gfilt_size=gfilt_size, background_gfilt_size=background_gfilt_size,
                                    filt_size=filt_size, min_edge_distance=min_edge_distance,
                                    use_dynamic_th=use_dynamic_th, dynamic_niters=dynamic_niters,

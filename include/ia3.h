@@ -203,6 +203,35 @@ int ia3_illumination_correct(const void* im_u16, int Z, int X, int Y, const void
 int ia3_bleedthrough_correct(const void* const* ims_u16, int C, int Z, int X, int Y, const void* profile,
                              int prof_dtype, void* const* outs_u16);
 
+/* ---- order statistics of a resident stack and illumination profiles ----------------------------------------------
+ * Exact selection (a radix select over the order-preserving key of the values; NaNs order last, as np.sort puts them).
+ * ia3_stack_order_stats_dev: out[i] (host, n values of the stack dtype) = np.sort(stack, axis=None)[ranks[i]];
+ * IA3_EINVAL for a rank outside [0, Z*X*Y) or n > 16. */
+int ia3_stack_order_stats_dev(const ia3_stack* s, const long long* ranks, int n, void* out);
+/* scipy.stats.scoreatpercentile(stack, per) as called at spot_tools/fitting.py:76 and
+ * correction_tools/illumination.py:186-187: idx = per / 100. * (n - 1), the order statistic idx when that is a whole
+ * number, else the two around it weighted in float64, (s[i] * w0 + s[i + 1] * w1) / (w0 + w1).  n <= 8 percentiles per
+ * call, each in [0, 100] (else IA3_EINVAL); out: n doubles on the host. */
+int ia3_stack_percentiles_dev(const ia3_stack* s, const double* pers, int n, double* out);
+/* out_dev (X*Y doubles, device) = np.sum(float64(stack), axis=0), planes added in z order; clip != 0: every voxel is
+ * first clamped to [lo, hi] as np.clip does (correction_tools/illumination.py:183-189). */
+int ia3_clip_sum_z_dev(const ia3_stack* s, int clip, double lo, double hi, double* out_dev);
+/* scipy.ndimage.gaussian_filter(float64 (X, Y) image, sigma, truncate=truncate, mode) in float64, bit for bit: axis 0
+ * then axis 1, NI_Correlate1D's summation order.  `weights` (2 * radius + 1 doubles) are the taps SciPy would use, made
+ * by NumPy on the caller's side (_lib.gaussian_taps) and used verbatim; NULL: they are made here from (sigma, truncate)
+ * with libm's exp, which differs from NumPy's in the last bit for some arguments, so only explicit taps promise
+ * bit-equal results.  mode reflect or nearest; radius up to 1024, larger ones IA3_EUNSUPPORTED.  out may be the input. */
+int ia3_gaussian_filter2d_f64_dev(const double* in_dev, int X, int Y, double sigma, double truncate, int mode,
+                                  const double* weights, int radius, double* out_dev);
+int ia3_gaussian_filter2d_f64(const double* in, int X, int Y, double sigma, double truncate, int mode,
+                              const double* weights, int radius, double* out);
+/* correction_tools/illumination.py:181-190 for one channel stack (uint16 or float32): with remove_cap the limits are
+ * the percentiles min(per_a, per_b) and max(per_a, per_b) of the stack; out_host (X*Y doubles) =
+ * gaussian_filter(sum_z clip(float64(im), limits), sigma), taps as above (truncate 4).  Runs on the calling thread's
+ * stream and waits for it. */
+int ia3_illumination_image_profile_dev(const ia3_stack* im, int remove_cap, double per_a, double per_b, double sigma,
+                                       const double* weights, int radius, double* out_host);
+
 /* ---- seeding: spot_tools/fitting.py:20-154 get_seeds ------------------------------------------ */
 typedef struct ia3_seed_params {
   double th_seed;               /* threshold on max_im - min_im */
