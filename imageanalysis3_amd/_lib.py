@@ -37,6 +37,7 @@ EXPORTS = [
     "ia3_align_image_dev", "ia3_process_movies", "ia3_drift_ref_create", "ia3_drift_ref_free", "ia3_align_image_ref",
     "ia3_stack_order_stats_dev", "ia3_stack_percentiles_dev", "ia3_clip_sum_z_dev",
     "ia3_gaussian_filter2d_f64_dev", "ia3_gaussian_filter2d_f64", "ia3_illumination_image_profile_dev",
+    "ia3_crop_pairs_dev", "ia3_poly_field_dev", "ia3_buffer_alloc", "ia3_buffer_download",
 ]
 
 
@@ -353,6 +354,62 @@ def gaussian_filter2d_f64(im, sigma, truncate=4.0, mode=MODE_REFLECT):
     check(lib().ia3_gaussian_filter2d_f64(dptr(a), a.shape[0], a.shape[1], C.c_double(float(sigma)),
                                           C.c_double(float(truncate)), int(mode), wp, r, dptr(out)))
     return out
+
+
+CROP_MAX = 15   # largest box of ia3_crop_pairs_dev along an axis
+
+
+def crop_pairs(stack_a, centers_a, crop, stack_b=None, centers_b=None, regress=False):
+    """``ia3_crop_pairs_dev``: the boxes ``crop_neighboring_area(stack, centre, crop)`` of the reference for every row of
+    ``centers_a`` on the resident ``stack_a`` (and of ``centers_b`` on ``stack_b``), one call for all of them.  Returns
+    ``(boxes_a, boxes_b, regression)``: (n,) + crop arrays of the stack dtype (``boxes_b`` None without a second stack) and,
+    with ``regress``, the float64 arrays ``(slope, intercept, rsq)`` of box b on box a, else None."""
+    crop = np.ascontiguousarray(crop, dtype=np.int32)
+    ca = np.ascontiguousarray(centers_a, dtype=np.float64).reshape(-1, 3)
+    n = len(ca)
+    shape = (n,) + tuple(int(c) for c in crop)
+    boxes_a = np.empty(shape, dtype=stack_a.dtype)
+    boxes_b, cb, reg = None, None, None
+    if stack_b is not None:
+        cb = np.ascontiguousarray(centers_b, dtype=np.float64).reshape(-1, 3)
+        if len(cb) != n:
+            raise ValueError("crop_pairs: %d centres for the first stack, %d for the second" % (n, len(cb)))
+        if tuple(stack_b.shape) != tuple(stack_a.shape) or np.dtype(stack_b.dtype) != np.dtype(stack_a.dtype):
+            raise ValueError("crop_pairs: the two stacks must have the same shape and dtype")
+        boxes_b = np.empty(shape, dtype=stack_b.dtype)
+    if regress:
+        reg = tuple(np.empty(n, dtype=np.float64) for _ in range(3))
+    check(lib().ia3_crop_pairs_dev(stack_a._h, None if stack_b is None else stack_b._h, dptr(ca),
+                                   None if cb is None else dptr(cb), n, crop.ctypes.data_as(C.POINTER(C.c_int)),
+                                   ptr(boxes_a), None if boxes_b is None else ptr(boxes_b),
+                                   *([dptr(r) for r in reg] if regress else [None, None, None])))
+    return boxes_a, boxes_b, reg
+
+
+def poly_columns(order):
+    """Columns of ``generate_polynomial_data`` for three coordinates and ``order``."""
+    order = int(order)
+    return (order + 1) * (order + 2) * (order + 3) // 6
+
+
+def poly_field(constants, orders, ref_center, shape, dtype=np.float64):
+    """``ia3_poly_field_dev``: device pointer (``c_void_p``, free with ``ia3_buffer_free``) of the (3,) + shape field of
+    the per-axis polynomial ``constants`` (chromatic.py:282-289), float64 or float32."""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("a polynomial field is float32 or float64, got %s" % dt)
+    if len(constants) != 3 or len(orders) != 3 or len(ref_center) != 3 or len(shape) != 3:
+        raise ValueError("a polynomial field takes three axes: constants, orders, ref_center and shape of length 3")
+    cs = [np.ascontiguousarray(c, dtype=np.float64).ravel() for c in constants]
+    flat = np.ascontiguousarray(np.concatenate(cs))
+    ncol = np.array([len(c) for c in cs], dtype=np.int32)
+    od = np.array([int(o) for o in orders], dtype=np.int32)
+    rc = np.ascontiguousarray(ref_center, dtype=np.float64)
+    p = C.c_void_p()
+    check(lib().ia3_poly_field_dev(dptr(flat), ncol.ctypes.data_as(C.POINTER(C.c_int)), od.ctypes.data_as(C.POINTER(C.c_int)),
+                                   dptr(rc), int(shape[0]), int(shape[1]), int(shape[2]), 1 if dt == np.float32 else 2,
+                                   C.byref(p)))
+    return p
 
 
 def profile_enable(on=True):

@@ -1,1 +1,3 @@
 """correction_tools — filter / alignment / translate operators (reference: correction_tools/)."""
+
+_drift_channel = '488'

@@ -24,6 +24,17 @@ def warp_3d_image(image, drift, chromatic_profile=None,
     if len(_drift) != 3:
         raise IndexError("drift should have 3 components (z,x,y)")
     field, fdt = None, 0
+    if hasattr(chromatic_profile, 'dtype_code') and hasattr(chromatic_profile, 'ptr'):
+        # a field that is already resident (io_tools.load.DeviceBuffer, e.g. chromatic_profile_from_constants)
+        if tuple(chromatic_profile.shape) != (3,) + a.shape:
+            raise IndexError(f"chromatic_profile shape {tuple(chromatic_profile.shape)} should be {(3,) + a.shape}")
+        with L.DeviceStack.upload(a) as _src, L.DeviceStack.empty(a.shape, a.dtype) as _dst:
+            L.check(L.lib().ia3_warp3d_dev(_src._h, L.dptr(_drift), chromatic_profile.ptr, chromatic_profile.dtype_code,
+                                           int(warp_order), _MODES[border_mode], C.c_double(float(np.min(a))), _dst._h))
+            out = _dst.download()
+        if verbose:
+            print(f"-- finish warp image in {time.time()-_start_time:.3f}s. ")
+        return out
     if chromatic_profile is not None:
         cp = np.asarray(chromatic_profile)
         if cp.shape != (3,) + a.shape:

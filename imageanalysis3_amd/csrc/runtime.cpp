@@ -760,6 +760,25 @@ int ia3_buffer_upload(const void* host, size_t bytes, void** devptr) {
   }
   return IA3_OK;
 }
+// the same kind of buffer, filled on the device (ia3_poly_field_dev); its contents are undefined until then
+int ia3_buffer_alloc(size_t bytes, void** devptr) {
+  int rc = ensure_init(); if (rc) return rc;
+  if (!devptr || bytes == 0) return set_error(IA3_EINVAL, "bad buffer arguments");
+  void* d = nullptr;
+  if (hipMalloc(&d, bytes) != hipSuccess) { (void)hipGetLastError(); return set_error(IA3_ENOMEM, "hipMalloc(%zu) failed", bytes); }
+  *devptr = d;
+  std::lock_guard<std::mutex> lk(g_mu);
+  g_const_bufs[d] = ConstNote();
+  return IA3_OK;
+}
+int ia3_buffer_download(const void* devptr, size_t bytes, void* host) {
+  int rc = ensure_init(); if (rc) return rc;
+  if (!devptr || !host || bytes == 0) return set_error(IA3_EINVAL, "bad buffer arguments");
+  IA3_HIP(hipStreamSynchronize(stream()));   // (as ia3_stack_download: what fills the buffer first, the copy afterwards)
+  IA3_HIP(hipMemcpyAsync(host, devptr, bytes, hipMemcpyDeviceToHost, stream()));
+  IA3_HIP(hipStreamSynchronize(stream()));
+  return IA3_OK;
+}
 void ia3_buffer_free(void* devptr) {
   if (devptr && g_pid == getpid()) {
     (void)hipStreamSynchronize(stream());

@@ -272,7 +272,8 @@ def split_im_by_channels(im, sel_channels, all_channels, single_im_size=None,
 
 
 class DeviceBuffer(object):
-    """A run-constant array (correction profile) resident in HBM."""
+    """A run-constant array (correction profile) resident in HBM: uploaded from ``arr``, or made on the device
+    (``DeviceBuffer.empty`` / ``DeviceBuffer.adopt``; ``arr`` is then None).  ``shape`` and ``dtype`` describe it either way."""
 
     def __init__(self, arr):
         self.arr = np.ascontiguousarray(arr)
@@ -280,9 +281,39 @@ class DeviceBuffer(object):
         if self.arr.dtype not in (np.float32, np.float64):
             self.arr = self.arr.astype(np.float64)
             self.dtype_code = 2
+        self.shape, self.dtype = tuple(self.arr.shape), self.arr.dtype
         p = C.c_void_p()
         L.check(L.lib().ia3_buffer_upload(L.ptr(self.arr), C.c_size_t(self.arr.nbytes), C.byref(p)))
         self.ptr = p
+
+    @classmethod
+    def adopt(cls, devptr, shape, dtype):
+        """Owner of a buffer the library made (``ia3_buffer_alloc``, ``ia3_poly_field_dev``): float32 or float64."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("a device buffer is float32 or float64, got %s" % dt)
+        self = cls.__new__(cls)
+        self.arr = None
+        self.shape, self.dtype = tuple(int(v) for v in shape), dt
+        self.dtype_code = 1 if dt == np.float32 else 2
+        self.ptr = devptr
+        return self
+
+    @classmethod
+    def empty(cls, shape, dtype=np.float64):
+        """A buffer of undefined contents, without a host array."""
+        dt = np.dtype(dtype)
+        if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise TypeError("a device buffer is float32 or float64, got %s" % dt)
+        p = C.c_void_p()
+        L.check(L.lib().ia3_buffer_alloc(C.c_size_t(int(np.prod(shape)) * dt.itemsize), C.byref(p)))
+        return cls.adopt(p, shape, dt)
+
+    def download(self):
+        """The buffer's contents as a new ndarray of ``shape`` and ``dtype``."""
+        out = np.empty(self.shape, dtype=self.dtype)
+        L.check(L.lib().ia3_buffer_download(self.ptr, C.c_size_t(out.nbytes), L.ptr(out)))
+        return out
 
     def free(self):
         if self.ptr is not None:
@@ -491,8 +522,8 @@ def correct_fov_image(dax_filename, sel_channels,
                 _field, _fdt = None, 0
                 if chromatic_corr and _ch in _chromatic_channels and chromatic_profile[_ch] is not None:
                     _fb = _as_buffer(chromatic_profile[_ch])
-                    if _fb.arr.shape != (3,) + tuple(_ims[_i].shape):
-                        raise IndexError(f"chromatic_profile[{_ch}] shape {_fb.arr.shape} should be "
+                    if tuple(_fb.shape) != (3,) + tuple(_ims[_i].shape):
+                        raise IndexError(f"chromatic_profile[{_ch}] shape {_fb.shape} should be "
                                          f"{(3,) + tuple(_ims[_i].shape)}")
                     _field, _fdt = _fb.ptr, _fb.dtype_code
                 _d = np.ascontiguousarray(_drift if _drift.any() else np.zeros(3), dtype=np.float64)
@@ -623,8 +654,8 @@ class MoviePlan(object):
                 if _ch not in illumination_profile:
                     raise KeyError(f"channel:{_ch} not given in illumination_profile")
                 _ip = _as_buffer(illumination_profile[_ch])
-                if tuple(_ip.arr.shape) != (X, Y):
-                    raise IndexError(f"illumination profile shape {_ip.arr.shape} should be {(X, Y)}")
+                if tuple(_ip.shape) != (X, Y):
+                    raise IndexError(f"illumination profile shape {_ip.shape} should be {(X, Y)}")
                 self._keep.append(_ip)
                 p.illum_profile[_i], p.illum_dtype[_i] = _ip.ptr.value, _ip.dtype_code
         if bleed_corr and len(_overlap_channels) > 0:
@@ -637,8 +668,8 @@ class MoviePlan(object):
                 bleed_profile = np.array(bleed_profile, dtype=np.float32)
             _bp = _as_buffer(bleed_profile)
             _nc = len(corr_channels)
-            if tuple(_bp.arr.shape) != (_nc, _nc, X, Y):
-                raise IndexError(f"Wrong input shape for bleed_profile: {_bp.arr.shape}, should be {(_nc, _nc, X, Y)}")
+            if tuple(_bp.shape) != (_nc, _nc, X, Y):
+                raise IndexError(f"Wrong input shape for bleed_profile: {_bp.shape}, should be {(_nc, _nc, X, Y)}")
             self._keep.append(_bp)
             p.n_bleed = _nc
             for _i, _ch in enumerate(corr_channels):
@@ -663,8 +694,8 @@ class MoviePlan(object):
             p.warp_always[_i] = 1 if _chrom else 0
             if _chrom and chromatic_profile[_ch] is not None:
                 _fb = _as_buffer(chromatic_profile[_ch])
-                if tuple(_fb.arr.shape) != (3, Z, X, Y):
-                    raise IndexError(f"chromatic_profile[{_ch}] shape {_fb.arr.shape} should be {(3, Z, X, Y)}")
+                if tuple(_fb.shape) != (3, Z, X, Y):
+                    raise IndexError(f"chromatic_profile[{_ch}] shape {_fb.shape} should be {(3, Z, X, Y)}")
                 self._keep.append(_fb)
                 p.chrom_field[_i], p.chrom_dtype[_i] = _fb.ptr.value, _fb.dtype_code
         if gaussian_highpass:

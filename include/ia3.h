@@ -164,6 +164,9 @@ int ia3_stack_deinterleave(const ia3_stack* raw, int start, int step, int Z, ia3
 /* device buffers for run-constant data (correction profiles) */
 int ia3_buffer_upload(const void* host, size_t bytes, void** devptr);
 void ia3_buffer_free(void* devptr);
+/* a buffer of the same kind with undefined contents (for results made on the device), and its copy to the host */
+int ia3_buffer_alloc(size_t bytes, void** devptr);
+int ia3_buffer_download(const void* devptr, size_t bytes, void* host);
 int ia3_stack_download(const ia3_stack* s, void* host);
 int ia3_stack_info(const ia3_stack* s, int* dtype, int* Z, int* X, int* Y, void** devptr);
 void ia3_stack_free(ia3_stack* s);
@@ -266,6 +269,26 @@ int ia3_dog_seed_dev(const ia3_stack* im, const ia3_seed_params* p,
  * to SciPy.  On stacks of 30 / 40 / 50 planes with the default sigmas (0.75, 7.5) the two axis-0 passes share one
  * launch; every other case runs the separate filters.  Outputs must not alias the input or each other. */
 int ia3_dog_filters_dev(const ia3_stack* im, double sigma_front, double sigma_back, ia3_stack* front, ia3_stack* back_axis0);
+
+/* ---- chromatic-aberration profile generation (correction_tools/chromatic.py:119-412) --------------------------------
+ * io_tools/crop.py:107-152 crop_neighboring_area(im, centre, crop, 'nearest') for n centres per resident stack, bit for
+ * bit: rough crop, map_coordinates(order 3) on it, output of the stack's dtype.  a, b: stacks of equal shape and dtype (b
+ * may be NULL: boxes of a alone); centers_a / centers_b: n x 3 float64 (z, x, y); crop[3]: box size per axis, 1..15
+ * (larger: IA3_EUNSUPPORTED); crops_*_host: n x crop[0] x crop[1] x crop[2] of the stack dtype.  slope / intercept / rsq
+ * (n doubles each, uint16 stacks only, else IA3_EUNSUPPORTED): the least-squares line box_b = slope * box_a + intercept
+ * and its coefficient of determination (chromatic.py:387-390) from exact integer sums; constant box_a: slope 0,
+ * intercept mean(box_b), rsq 0; constant box_b: rsq 1.  Every output pointer may be NULL.  A centre whose rough crop
+ * does not meet the image is IA3_EINVAL. */
+int ia3_crop_pairs_dev(const ia3_stack* a, const ia3_stack* b, const double* centers_a, const double* centers_b, int n,
+                       const int* crop, void* crops_a_host, void* crops_b_host, double* slope, double* intercept,
+                       double* rsq);
+/* chromatic.py:282-289: *devptr = new buffer (free with ia3_buffer_free) holding the (3, Z, X, Y) field
+ * out[a, z, x, y] = sum_k C_a[k] * m_k(z - ref_center[0], x - ref_center[1], y - ref_center[2]), m = the columns of
+ * generate_polynomial_data(., orders[a]), summed left to right in float64 and stored as out_dtype (1 = float32,
+ * 2 = float64: what ia3_warp3d_dev takes).  consts: the constants of axis 0, 1, 2 one after the other, n_cols[a] of
+ * them (1, 4, 10, 20 for orders 0..3; higher orders: IA3_EUNSUPPORTED). */
+int ia3_poly_field_dev(const double* consts, const int* n_cols, const int* orders, const double* ref_center, int Z, int X,
+                       int Y, int out_dtype, void** devptr);
 
 /* ---- the pre-correction chain of io_tools/load.py:323-384 on stacks that stay resident ---------------------------
  * ia3_remove_hot_pixels_dev works in place; float_arith != 0 on a uint16 stack = the chain's
