@@ -12,7 +12,8 @@ def Z_Shift_Correction(im, dtype=np.uint16, normalization=False, verbose=False):
     """corrections.py:479-487 — ``im / median_z[:,None,None] * median(im)`` cast to ``dtype``.
     (Both branches of ``normalization`` are identical in the reference.)  The float32 arithmetic of the
     production call ``Z_Shift_Correction(im.astype(np.float32), dtype=np.uint16)`` (io_tools/load.py:342)
-    runs on the device; medians by radix select."""
+    runs on the device; medians by radix select.  A float32 stack that holds NaN is not supported: ``np.median``
+    returns NaN there, while the radix select sorts NaN last (the chain only ever passes uint16 frames)."""
     if verbose:
         print("-- correcting Z axis illumination shifts.")
     a = L.as_stack_array(im)

@@ -216,7 +216,8 @@ static void launch_bleed(int prof_dtype, unsigned gx, hipStream_t st, const Chan
 
 // ---- DaxProcesser variants (classes/preprocess.py:464-680): same stages with a min-max rescale to the full uint16
 // range.  Two passes over the inputs: (1) the corrected value of every voxel is formed and only its min / max are
-// kept (fixed grid of partials + one block; min/max do not depend on the order), (2) it is formed again, rescaled
+// kept (fixed grid of partials + one block; min/max do not depend on the order, and any NaN makes both NaN as in
+// np.min / np.max), (2) it is formed again, rescaled
 // exactly as NumPy evaluates `(im - min) / (max - min) * 65535 + 0`, clipped and truncated to uint16.
 constexpr int MM_BLOCKS = 1024;
 template <class P> __device__ __forceinline__ P illum_val(const uint16_t* im, const P* prof, size_t z, size_t plane, size_t i) {
@@ -228,14 +229,18 @@ template <class P> __device__ __forceinline__ double bleed_val(const ChanPtrs& c
   return acc;
 }
 struct MinMax { double mn, mx; };
+// np.min / np.max propagate NaN: a NaN candidate replaces the running value, and a NaN running value stays (both
+// comparisons are false for it).  Without NaN these are the plain `a < b ? a : b` / `a > b ? a : b`.
+template <class V> __device__ __forceinline__ V nan_min(V q, V mn) { return (q < mn || q != q) ? q : mn; }
+template <class V> __device__ __forceinline__ V nan_max(V q, V mx) { return (q > mx || q != q) ? q : mx; }
 template <class V> __device__ __forceinline__ void block_minmax(V mn, V mx, MinMax* part) {
   __shared__ double smn[256], smx[256];
   smn[threadIdx.x] = (double)mn; smx[threadIdx.x] = (double)mx;
   __syncthreads();
   for (int k = 128; k > 0; k >>= 1) {
     if ((int)threadIdx.x < k) {
-      smn[threadIdx.x] = smn[threadIdx.x + k] < smn[threadIdx.x] ? smn[threadIdx.x + k] : smn[threadIdx.x];
-      smx[threadIdx.x] = smx[threadIdx.x + k] > smx[threadIdx.x] ? smx[threadIdx.x + k] : smx[threadIdx.x];
+      smn[threadIdx.x] = nan_min(smn[threadIdx.x + k], smn[threadIdx.x]);
+      smx[threadIdx.x] = nan_max(smx[threadIdx.x + k], smx[threadIdx.x]);
     }
     __syncthreads();
   }
@@ -247,7 +252,7 @@ __global__ __launch_bounds__(256) void illum_minmax_k(const uint16_t* __restrict
   const size_t n = plane * Z;
   for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (size_t)MM_BLOCKS * 256) {
     const P q = illum_val<P>(im, prof, v / plane, plane, v % plane);
-    mn = q < mn ? q : mn; mx = q > mx ? q : mx;
+    mn = nan_min(q, mn); mx = nan_max(q, mx);
   }
   block_minmax(mn, mx, part);
 }
@@ -257,7 +262,7 @@ __global__ __launch_bounds__(256) void bleed_minmax_k(ChanPtrs ch, int C, int a,
   const size_t n = plane * Z;
   for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < n; v += (size_t)MM_BLOCKS * 256) {
     const double q = bleed_val<P>(ch, C, a, prof, v / plane, plane, v % plane);
-    mn = q < mn ? q : mn; mx = q > mx ? q : mx;
+    mn = nan_min(q, mn); mx = nan_max(q, mx);
   }
   block_minmax(mn, mx, part);
 }
@@ -268,8 +273,8 @@ __global__ __launch_bounds__(1024) void minmax_final_k(const MinMax* __restrict_
   __syncthreads();
   for (int k = 512; k > 0; k >>= 1) {
     if ((int)threadIdx.x < k) {
-      smn[threadIdx.x] = smn[threadIdx.x + k] < smn[threadIdx.x] ? smn[threadIdx.x + k] : smn[threadIdx.x];
-      smx[threadIdx.x] = smx[threadIdx.x + k] > smx[threadIdx.x] ? smx[threadIdx.x + k] : smx[threadIdx.x];
+      smn[threadIdx.x] = nan_min(smn[threadIdx.x + k], smn[threadIdx.x]);
+      smx[threadIdx.x] = nan_max(smx[threadIdx.x + k], smx[threadIdx.x]);
     }
     __syncthreads();
   }
