@@ -37,7 +37,7 @@ EXPORTS = [
     "ia3_align_image_dev", "ia3_process_movies", "ia3_drift_ref_create", "ia3_drift_ref_free", "ia3_align_image_ref",
     "ia3_stack_order_stats_dev", "ia3_stack_percentiles_dev", "ia3_clip_sum_z_dev",
     "ia3_gaussian_filter2d_f64_dev", "ia3_gaussian_filter2d_f64", "ia3_illumination_image_profile_dev",
-    "ia3_crop_pairs_dev", "ia3_poly_field_dev", "ia3_buffer_alloc", "ia3_buffer_download",
+    "ia3_crop_pairs_dev", "ia3_poly_field_dev", "ia3_buffer_alloc", "ia3_buffer_download", "ia3_bleedthrough_profile_dev",
 ]
 
 
@@ -409,6 +409,38 @@ def poly_field(constants, orders, ref_center, shape, dtype=np.float64):
     check(lib().ia3_poly_field_dev(dptr(flat), ncol.ctypes.data_as(C.POINTER(C.c_int)), od.ctypes.data_as(C.POINTER(C.c_int)),
                                    dptr(rc), int(shape[0]), int(shape[1]), int(shape[2]), 1 if dt == np.float32 else 2,
                                    C.byref(p)))
+    return p
+
+
+def bleedthrough_profile(consts, present, order, ref_center, shape, mean_z=True, invert=True, dtype=np.float64):
+    """``ia3_bleedthrough_profile_dev``: device pointer (``c_void_p``, for ``DeviceBuffer.adopt``) of the (C, C, X, Y)
+    (``mean_z``) or (C, C, Z, X, Y) bleedthrough profile of bleedthrough.py:451-486.  ``consts``: (C, C, n_cols) float64,
+    ``consts[tar, ref]`` the polynomial of the slope profile from channel ref into channel tar; ``present``: (C, C), 0 for
+    a direction whose profile is zero; the diagonal is 1 whatever is given there.  ``invert``: every C x C matrix is
+    replaced by its inverse; ``np.linalg.LinAlgError("Singular matrix")`` when one has a zero pivot, as ``np.linalg.inv``
+    raises for the first such pixel (``.n_singular`` holds their number)."""
+    dt = np.dtype(dtype)
+    if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise TypeError("a bleedthrough profile is float32 or float64, got %s" % dt)
+    cs = np.ascontiguousarray(consts, dtype=np.float64)
+    pr = np.ascontiguousarray(np.asarray(present) != 0, dtype=np.uint8)
+    if cs.ndim != 3 or cs.shape[0] != cs.shape[1] or pr.shape != cs.shape[:2]:
+        raise ValueError("a bleedthrough profile takes (C, C, n_cols) constants and a (C, C) present table")
+    order = int(order)
+    if 0 <= order <= 3 and cs.shape[2] != poly_columns(order):
+        raise ValueError("%d constants given for order %d, %d expected" % (cs.shape[2], order, poly_columns(order)))
+    if len(ref_center) != 3 or len(shape) != 3:
+        raise ValueError("a bleedthrough profile takes ref_center and shape of the three axes z, x, y")
+    rc = np.ascontiguousarray(ref_center, dtype=np.float64)
+    p, ns = C.c_void_p(), C.c_longlong(0)
+    check(lib().ia3_bleedthrough_profile_dev(dptr(cs), pr.ctypes.data_as(C.POINTER(C.c_ubyte)), int(cs.shape[0]), order, dptr(rc),
+                                            int(shape[0]), int(shape[1]), int(shape[2]), 1 if mean_z else 0,
+                                            1 if invert else 0, 1 if dt == np.float32 else 2, C.byref(p), C.byref(ns)))
+    if ns.value > 0:
+        lib().ia3_buffer_free(p)
+        err = np.linalg.LinAlgError("Singular matrix")
+        err.n_singular = int(ns.value)
+        raise err
     return p
 
 

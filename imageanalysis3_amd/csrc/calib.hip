@@ -14,6 +14,9 @@
 // poly_field_k   the dense (3, Z, X, Y) polynomial displacement field of chromatic.py:282-289: per axis the sum, left to
 //                right over the columns of generate_polynomial_data, of C[k] * monomial_k(z - r0, x - r1, y - r2) in
 //                float64.  A pure store stream.
+// bleed_profile_k  the tail of the bleedthrough generator (correction_tools/bleedthrough.py:451-486): per pixel the
+//                C x C matrix of slope polynomials (diagonal 1), its mean over z (sequential sum divided by Z) and its
+//                inverse by Gaussian elimination with partial pivoting, all in registers.  Reads nothing.
 // Compiled with -ffp-contract=off.
 #include "ia3_rt.h"
 #include <math.h>
@@ -295,6 +298,165 @@ int poly_field_launch(const PolyArgs& p, int Z, int X, int Y, F* out) {
   return IA3_OK;
 }
 
+// ---- bleedthrough profile ------------------------------------------------------------------------------------------
+constexpr int BLEED_MAXC = 4;
+constexpr int BLEED_MAXOFF = BLEED_MAXC * BLEED_MAXC - BLEED_MAXC;
+// off-diagonal entries in row-major order of (tar, ref); an absent one (present == 0) has ncol 0 and stays 0.0
+struct BleedArgs {
+  double C[BLEED_MAXOFF][POLY_MAXCOL];
+  int ncol;                      // columns of the fitting order
+  unsigned char present[BLEED_MAXOFF];
+  double ref[3];
+};
+
+// A (row-major N x N) <- its inverse by Gauss-Jordan elimination with partial pivoting, pivot = first row of largest
+// magnitude in the column; false (A all NaN) where a pivot is zero or NaN.  Fully unrolled: A stays in registers.
+template <int N>
+__device__ __forceinline__ bool invert_gepp(double* A) {
+  double B[N * N];
+#pragma unroll
+  for (int i = 0; i < N; ++i)
+#pragma unroll
+    for (int j = 0; j < N; ++j) B[i * N + j] = i == j ? 1.0 : 0.0;
+  bool ok = true;
+#pragma unroll
+  for (int c = 0; c < N; ++c) {
+    double best = fabs(A[c * N + c]);
+    int piv = c;
+#pragma unroll
+    for (int r = c + 1; r < N; ++r) {
+      const double v = fabs(A[r * N + c]);
+      if (v > best) { best = v; piv = r; }
+    }
+#pragma unroll
+    for (int r = c + 1; r < N; ++r) {   // (selects, not indexed moves: the rows stay in registers)
+      const bool sw = piv == r;
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        const double a0 = A[c * N + j], a1 = A[r * N + j], b0 = B[c * N + j], b1 = B[r * N + j];
+        A[c * N + j] = sw ? a1 : a0; A[r * N + j] = sw ? a0 : a1;
+        B[c * N + j] = sw ? b1 : b0; B[r * N + j] = sw ? b0 : b1;
+      }
+    }
+    const double p = A[c * N + c];
+    ok = ok && (p != 0.0) && (p == p);
+#pragma unroll
+    for (int r = 0; r < N; ++r) {
+      if (r == c) continue;
+      const double f = A[r * N + c] / p;
+#pragma unroll
+      for (int j = 0; j < N; ++j) {
+        A[r * N + j] = A[r * N + j] - f * A[c * N + j];
+        B[r * N + j] = B[r * N + j] - f * B[c * N + j];
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < N; ++i) {
+    const double d = A[i * N + i];
+#pragma unroll
+    for (int j = 0; j < N; ++j) A[i * N + j] = ok ? B[i * N + j] / d : __builtin_nan("");
+  }
+  return ok;
+}
+
+// V consecutive y per thread, as poly_field_k.  MEANZ: the thread sums z = 0..Z-1 in order and divides by Z, output
+// (N, N, X, Y); else blockIdx.z is z, output (N, N, Z, X, Y).
+template <class F, int N, int V, bool MEANZ>
+__global__ __launch_bounds__(256) void bleed_profile_k(BleedArgs p, int Z, int X, int Y, int invert, F* __restrict__ out,
+                                                       unsigned long long* __restrict__ n_singular) {
+  const int y0 = (blockIdx.x * 256 + threadIdx.x) * V;
+  if (y0 >= Y) return;
+  const int x = blockIdx.y;
+  const size_t plane = MEANZ ? (size_t)X * Y : (size_t)Z * X * Y;
+  const size_t o = MEANZ ? (size_t)x * Y + y0 : ((size_t)blockIdx.z * X + x) * Y + y0;
+  const int zlo = MEANZ ? 0 : (int)blockIdx.z, zhi = MEANZ ? Z : (int)blockIdx.z + 1;
+  const double v1 = (double)x - p.ref[1];
+  double A[V][N * N];
+#pragma unroll
+  for (int e = 0; e < V; ++e)
+#pragma unroll
+    for (int q = 0; q < N * N; ++q) A[e][q] = 0.0;
+  for (int z = zlo; z < zhi; ++z) {
+    const double v0 = (double)z - p.ref[0];
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      double m[POLY_MAXCOL];
+      monomials(v0, v1, (double)(y0 + e) - p.ref[2], m);
+#pragma unroll
+      for (int t = 0; t < N; ++t)
+#pragma unroll
+        for (int r = 0; r < N; ++r) {
+          if (t == r) { A[e][t * N + r] = A[e][t * N + r] + 1.0; continue; }
+          const int k0 = t * (N - 1) + (r < t ? r : r - 1);   // index among the off-diagonal entries
+          double s = 0.0;
+          if (p.present[k0]) {
+            s = p.C[k0][0] * m[0];
+#pragma unroll
+            for (int k = 1; k < POLY_MAXCOL; ++k)
+              if (k < p.ncol) s = s + p.C[k0][k] * m[k];
+          }
+          A[e][t * N + r] = A[e][t * N + r] + s;
+        }
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    if constexpr (MEANZ) {
+      const double dz = (double)Z;
+#pragma unroll
+      for (int q = 0; q < N * N; ++q) A[e][q] = A[e][q] / dz;
+    }
+    if (invert && !invert_gepp<N>(A[e])) atomicAdd(n_singular, 1ull);
+  }
+#pragma unroll
+  for (int q = 0; q < N * N; ++q) {
+    if constexpr (V == 1) {
+      out[q * plane + o] = (F)A[0][q];
+    } else {
+      typedef F vec __attribute__((ext_vector_type(V)));
+      vec w;
+#pragma unroll
+      for (int e = 0; e < V; ++e) w[e] = (F)A[e][q];
+      *(vec*)(out + q * plane + o) = w;
+    }
+  }
+}
+
+template <class F, int N, bool MEANZ>
+int bleed_profile_launch(const BleedArgs& p, int Z, int X, int Y, int invert, F* out, unsigned long long* n_singular) {
+  // 16 bytes of a row per thread where the registers hold it.  In the z loop the compiler keeps the z-invariant products
+  // (10 of the 20 columns per entry) in registers, N * N - N entries per pixel: N = 3 holds two pixels without scratch,
+  // N = 4 one (kernel-resource-usage remarks of hipcc, gfx950)
+  constexpr int FULL = 16 / (int)sizeof(F);
+  constexpr int VEC = !MEANZ || N == 2 ? FULL : (N == 3 ? 2 : 1);
+  hipStream_t st = stream();
+  ProfScope ps("bleed_profile");
+  const unsigned gz = MEANZ ? 1u : (unsigned)Z;
+  // a vector store is aligned only if Y and with it every plane offset is a multiple of 16 bytes
+  if (Y % (16 / (int)sizeof(F)) == 0)
+    hipLaunchKernelGGL((bleed_profile_k<F, N, VEC, MEANZ>), dim3((unsigned)((Y / VEC + 255) / 256), (unsigned)X, gz), dim3(256), 0,
+                       st, p, Z, X, Y, invert, out, n_singular);
+  else
+    hipLaunchKernelGGL((bleed_profile_k<F, N, 1, MEANZ>), dim3((unsigned)((Y + 255) / 256), (unsigned)X, gz), dim3(256), 0, st, p,
+                       Z, X, Y, invert, out, n_singular);
+  IA3_KCHECK();
+  return IA3_OK;
+}
+
+template <class F, int N>
+int bleed_profile_n(const BleedArgs& p, int Z, int X, int Y, int mean_z, int invert, F* out, unsigned long long* ns) {
+  return mean_z ? bleed_profile_launch<F, N, true>(p, Z, X, Y, invert, out, ns)
+                : bleed_profile_launch<F, N, false>(p, Z, X, Y, invert, out, ns);
+}
+
+template <class F>
+int bleed_profile_t(const BleedArgs& p, int C, int Z, int X, int Y, int mean_z, int invert, F* out, unsigned long long* ns) {
+  if (C == 2) return bleed_profile_n<F, 2>(p, Z, X, Y, mean_z, invert, out, ns);
+  if (C == 3) return bleed_profile_n<F, 3>(p, Z, X, Y, mean_z, invert, out, ns);
+  return bleed_profile_n<F, 4>(p, Z, X, Y, mean_z, invert, out, ns);
+}
+
 template <class T>
 int crop_pairs_t(const ia3_stack* a, const ia3_stack* b, const double* ca, const double* cb, int n, const int* crop,
                  void* crops_a, void* crops_b, double* slope, double* icpt, double* rsq) {
@@ -406,6 +568,51 @@ int ia3_poly_field_dev(const double* consts, const int* n_cols, const int* order
   rc = out_dtype == 1 ? poly_field_launch<float>(p, Z, X, Y, (float*)d) : poly_field_launch<double>(p, Z, X, Y, (double*)d);
   if (!rc && hipStreamSynchronize(stream()) != hipSuccess) rc = set_error(IA3_EHIP, "polynomial field kernel failed");
   if (rc) { ia3_buffer_free(d); return rc; }
+  *devptr = d;
+  return IA3_OK;
+}
+
+int ia3_bleedthrough_profile_dev(const double* consts, const unsigned char* present, int C, int order,
+                                 const double* ref_center, int Z, int X, int Y, int mean_z, int invert, int out_dtype,
+                                 void** devptr, long long* n_singular) {
+  int rc = ensure_init(); if (rc) return rc;
+  if (!consts || !present || !ref_center || !devptr || !n_singular) return set_error(IA3_EINVAL, "null argument");
+  if (C < 2 || order < 0) return set_error(IA3_EINVAL, "bad channel count %d or fitting order %d", C, order);
+  if (C > BLEED_MAXC) return set_error(IA3_EUNSUPPORTED, "%d channels: 2 to %d are built", C, BLEED_MAXC);
+  if (order > 3) return set_error(IA3_EUNSUPPORTED, "fitting order %d: orders 0 to 3 are built", order);
+  if (Z < 1 || X < 1 || Y < 1 || Z > 65535 || X > 65535) return set_error(IA3_EINVAL, "bad profile shape (%d,%d,%d)", Z, X, Y);
+  if (out_dtype != 1 && out_dtype != 2) return set_error(IA3_EINVAL, "profile dtype must be float32 (1) or float64 (2)");
+  BleedArgs p;
+  const int ncol = poly_cols(order);
+  p.ncol = ncol;
+  for (int k = 0; k < BLEED_MAXOFF; ++k) {
+    p.present[k] = 0;
+    for (int j = 0; j < POLY_MAXCOL; ++j) p.C[k][j] = 0.0;
+  }
+  for (int t = 0; t < C; ++t)
+    for (int r = 0; r < C; ++r) {
+      if (t == r) continue;
+      const int k0 = t * (C - 1) + (r < t ? r : r - 1);
+      p.present[k0] = present[t * C + r] ? 1 : 0;
+      for (int j = 0; j < ncol; ++j) p.C[k0][j] = consts[(size_t)(t * C + r) * ncol + j];
+    }
+  for (int a = 0; a < 3; ++a) p.ref[a] = ref_center[a];
+  const size_t bytes = (size_t)C * C * (mean_z ? 1 : Z) * X * Y * (out_dtype == 1 ? 4 : 8);
+  Scratch cnt(sizeof(unsigned long long));
+  if (!cnt.p) return IA3_ENOMEM;
+  hipStream_t st = stream();
+  IA3_HIP(hipMemsetAsync(cnt.p, 0, sizeof(unsigned long long), st));
+  void* d = nullptr;
+  rc = ia3_buffer_alloc(bytes, &d); if (rc) return rc;
+  unsigned long long* ns = cnt.as<unsigned long long>();
+  rc = out_dtype == 1 ? bleed_profile_t<float>(p, C, Z, X, Y, mean_z, invert, (float*)d, ns)
+                      : bleed_profile_t<double>(p, C, Z, X, Y, mean_z, invert, (double*)d, ns);
+  unsigned long long h = 0;
+  if (!rc && (hipMemcpyAsync(&h, cnt.p, sizeof(h), hipMemcpyDeviceToHost, st) != hipSuccess ||
+              hipStreamSynchronize(st) != hipSuccess))
+    rc = set_error(IA3_EHIP, "bleedthrough profile kernel failed");
+  if (rc) { ia3_buffer_free(d); return rc; }
+  *n_singular = (long long)h;
   *devptr = d;
   return IA3_OK;
 }

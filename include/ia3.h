@@ -290,6 +290,20 @@ int ia3_crop_pairs_dev(const ia3_stack* a, const ia3_stack* b, const double* cen
 int ia3_poly_field_dev(const double* consts, const int* n_cols, const int* orders, const double* ref_center, int Z, int X,
                        int Y, int out_dtype, void** devptr);
 
+/* ---- bleedthrough profile generation (correction_tools/bleedthrough.py:451-486) -------------------------------------
+ * consts: C*C blocks of n_cols doubles, block [tar*C + ref] = the polynomial of the slope profile from channel ref into
+ * channel tar (columns of generate_polynomial_data(., order), 1/4/10/20 for order 0..3); present[tar*C + ref] == 0: the
+ * zero profile (interploate_... returned np.zeros: not enough spots); diagonal blocks are ignored, the diagonal is 1.
+ * M[tar, ref](z, x, y) = sum_k c_k m_k(z - rc0, x - rc1, y - rc2), summed left to right in float64.  mean_z != 0
+ * (generate_2d): M is summed over z = 0..Z-1 in that order and divided by Z (what ndarray.mean(2) does), output
+ * (C, C, X, Y); else output (C, C, Z, X, Y).  invert != 0: every C x C matrix is replaced by its inverse
+ * (np.linalg.inv: elimination with partial pivoting); *n_singular = matrices with a zero pivot (their entries are NaN).
+ * out_dtype 1 float32, 2 float64.  C 2..4, order 0..3, else IA3_EUNSUPPORTED.  *devptr: new buffer of the ia3_buffer_*
+ * family. */
+int ia3_bleedthrough_profile_dev(const double* consts, const unsigned char* present, int C, int order,
+                                 const double* ref_center, int Z, int X, int Y, int mean_z, int invert,
+                                 int out_dtype, void** devptr, long long* n_singular);
+
 /* ---- the pre-correction chain of io_tools/load.py:323-384 on stacks that stay resident ---------------------------
  * ia3_remove_hot_pixels_dev works in place; float_arith != 0 on a uint16 stack = the chain's
  * corrections.Remove_Hot_Pixels(im.astype(np.float32), dtype=np.uint16) (float32 votes and means, one truncation at
