@@ -6,9 +6,10 @@
 //                  a. rough crop  [max(0, floor(c - crop/2)), min(size, ceil(c + crop/2)))
 //                  b. positions   idx + ((c - left) - (crop - 1)/2), float64, in this order
 //                  c. map_coordinates(order=3, mode='nearest') of the rough crop: edge-padded by 12, cubic B-spline
-//                     prefilter along axes 0, 1, 2 in float64 (warp.hip: same pole, gain, causal start and two sweeps; a
+//                     prefilter along axes 0, 1, 2 in float64 (ia3_spline.h: the start sum and the two sweeps of the warp; a
 //                     padded line has at most 41 samples, z^n is far from underflow and the start sum is SciPy's full one),
 //                     the position + 12 clamped to the padded array, 4 x 4 x 4 taps in C order with clamped indices
+//                     (ia3_spline.h: weights and sum)
 //                  d. uint16: floor(t + 0.5) clamped; float32: cast
 //                The padded coefficient volume of a pair (at most 41^3 doubles) lives in a slab of the workspace cache.
 // poly_field_k   the dense (3, Z, X, Y) polynomial displacement field of chromatic.py:282-289: per axis the sum, left to
@@ -23,23 +24,20 @@
 
 using namespace ia3rt;
 
-#include "warp_iir0_kernel.inc"
-using ia3warpk::NPAD;
-using ia3warpk::clampi;
+#include "ia3_spline.h"
+using namespace ia3spline;
 
 namespace {
 
-#define IA3_POLE3 (-0.26794919243112270647)   // as in warp.hip
 constexpr int CROP_MAX = 15;
 constexpr int ROUGH_MAX = CROP_MAX + 2;           // ceil(c + crop/2) - floor(c - crop/2) <= crop + 1 (+ 1: rounding of the two sums)
 constexpr int PADLEN_MAX = ROUGH_MAX + 2 * NPAD;    // 41
 constexpr int PADLEN_MIN = 1 + 2 * NPAD;            // 25
 
-// what the prefilter needs per padded line length n (index n - PADLEN_MIN), made on the host with the host's pow as
-// warp.hip's make_init makes it: zn = z^n, scale = z / (1 - zn^2); gain = (1 - z)(1 - 1/z)
+// what the prefilter needs per padded line length n (index n - PADLEN_MIN), made on the host (iir_init): the start sum is
+// the full one at these lengths, bound and amax_bits are not read
 struct SplineTab {
-  double gain;
-  double zn[PADLEN_MAX - PADLEN_MIN + 1], scale[PADLEN_MAX - PADLEN_MIN + 1];
+  IirInit q[PADLEN_MAX - PADLEN_MIN + 1];
 };
 
 struct CropGeom {
@@ -63,50 +61,6 @@ __host__ __device__ inline bool crop_geometry(const double* c, const int* crop, 
   return ok;
 }
 
-template <class T> __device__ __forceinline__ T out_cvt(double t);
-template <> __device__ __forceinline__ float out_cvt<float>(double t) { return (float)t; }
-template <> __device__ __forceinline__ uint16_t out_cvt<uint16_t>(double t) {
-  t = t > 0 ? t + 0.5 : 0.0;
-  t = t > 65535.0 ? 65535.0 : t;
-  return (uint16_t)(int)t;
-}
-
-// x / 6.0 correctly rounded (warp.hip: div6)
-__device__ __forceinline__ double div6(double x) {
-  const double y = 0x1.5555555555555p-3;
-  const double q = x * y;
-  const double r = __builtin_fma(-6.0, q, x);
-  return __builtin_fma(r, y, q);
-}
-
-// the cubic prefilter of one strided line in place: warp.hip's iir_start_strided (full sum) and its two sweeps
-__device__ __forceinline__ void spline_line(double* c, int stride, int n, double g, double zn, double scale) {
-  const double z = IA3_POLE3;
-  const double c0 = c[0] * g;
-  double s = c0 + zn * (c[(n - 1) * stride] * g);
-  double zi = z;
-  for (int i = 1; i < n; ++i) {
-    s += zi * (c[i * stride] * g + zn * (c[(n - 1 - i) * stride] * g));
-    zi *= z;
-  }
-  s *= scale;
-  s += c0;
-  double prev = s;
-  c[0] = prev;
-  for (int i = 1; i < n; ++i) {
-    const double v = c[i * stride] * g + z * prev;
-    c[i * stride] = v;
-    prev = v;
-  }
-  prev = prev * (z / (z - 1.0));
-  c[(n - 1) * stride] = prev;
-  for (int i = n - 2; i >= 0; --i) {
-    const double v = z * (prev - c[i * stride]);
-    c[i * stride] = v;
-    prev = v;
-  }
-}
-
 // one box of one stack; every thread of the workgroup takes part.  P: this workgroup's slab (>= the padded rough crop)
 template <class T>
 __device__ void crop_box(const T* __restrict__ im, int Z, int X, int Y, const double* __restrict__ centre, const int* crop,
@@ -125,16 +79,19 @@ __device__ void crop_box(const T* __restrict__ im, int Z, int X, int Y, const do
     P[i] = (double)im[((size_t)sz * X + sx) * Y + sy];
   }
   __syncthreads();
-  for (int p = tid; p < plane; p += 256)
-    spline_line(P + p, plane, n0, tab.gain, tab.zn[n0 - PADLEN_MIN], tab.scale[n0 - PADLEN_MIN]);
+  // the cubic prefilter of one strided line in place
+  auto spline_line = [&](double* c, int stride, int n) {
+    const IirInit& q = tab.q[n - PADLEN_MIN];
+    iir_two_sweeps_strided(c, (size_t)stride, 0, n, iir_start_strided(c, (size_t)stride, n, q), q.z, q.gain);
+  };
+  for (int p = tid; p < plane; p += 256) spline_line(P + p, plane, n0);
   __syncthreads();
   for (int p = tid; p < n0 * n2; p += 256) {
     const int z = p / n2, y = p - z * n2;
-    spline_line(P + z * plane + y, n2, n1, tab.gain, tab.zn[n1 - PADLEN_MIN], tab.scale[n1 - PADLEN_MIN]);
+    spline_line(P + z * plane + y, n2, n1);
   }
   __syncthreads();
-  for (int p = tid; p < n0 * n1; p += 256)
-    spline_line(P + p * n2, 1, n2, tab.gain, tab.zn[n2 - PADLEN_MIN], tab.scale[n2 - PADLEN_MIN]);
+  for (int p = tid; p < n0 * n1; p += 256) spline_line(P + p * n2, 1, n2);
   __syncthreads();
   const int np[3] = {n0, n1, n2};
   const int cvol = crop[0] * crop[1] * crop[2];
@@ -148,29 +105,12 @@ __device__ void crop_box(const T* __restrict__ im, int Z, int X, int Y, const do
       cc = cc + (double)NPAD;
       cc = cc < 0.0 ? 0.0 : (cc > (double)(np[a] - 1) ? (double)(np[a] - 1) : cc);   // mode 'nearest' on the padded array
       const double fl = floor(cc);
-      const double yv = cc - fl, zv = 1.0 - yv;
-      w[a][1] = div6(yv * yv * (yv - 2.0) * 3.0 + 4.0);
-      w[a][2] = div6(zv * zv * (zv - 2.0) * 3.0 + 4.0);
-      w[a][0] = div6(zv * zv * zv);
-      w[a][3] = 1.0 - w[a][0] - w[a][1] - w[a][2];
+      cubic_weights(cc - fl, w[a]);
       const int st = (int)fl - 1;
 #pragma unroll
       for (int k = 0; k < 4; ++k) idx[a][k] = clampi(st + k, np[a]);
     }
-    double t = 0.0;
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const double* row = P + idx[0][i] * plane + idx[1][j] * n2;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          double v = row[idx[2][k]];
-          v = v * w[0][i]; v = v * w[1][j]; v = v * w[2][k];
-          t = t + v;
-        }
-      }
-    out[o] = out_cvt<T>(t);
+    out[o] = out_cvt<T>(gather64([&](int i0, int i1) { return (const double*)P + i0 * plane + i1 * n2; }, idx, w));
   }
   __syncthreads();
 }
@@ -465,12 +405,7 @@ int crop_pairs_t(const ia3_stack* a, const ia3_stack* b, const double* ca, const
   const size_t cvol = (size_t)crop[0] * crop[1] * crop[2];
   const size_t slab = (size_t)(crop[0] + 2 + 2 * NPAD) * (crop[1] + 2 + 2 * NPAD) * (crop[2] + 2 + 2 * NPAD);
   SplineTab tab;
-  tab.gain = (1.0 - IA3_POLE3) * (1.0 - 1.0 / IA3_POLE3);
-  for (int len = PADLEN_MIN; len <= PADLEN_MAX; ++len) {
-    const double zn = pow(IA3_POLE3, (double)len);
-    tab.zn[len - PADLEN_MIN] = zn;
-    tab.scale[len - PADLEN_MIN] = IA3_POLE3 / (1.0 - zn * zn);
-  }
+  for (int len = PADLEN_MIN; len <= PADLEN_MAX; ++len) tab.q[len - PADLEN_MIN] = iir_init(len);
   // pairs per launch: slabs of at most 512 MB at a time
   const size_t fit = ((size_t)512 << 20) / (slab * sizeof(double));
   const int per = fit < (size_t)n ? (int)fit : n;

@@ -15,6 +15,8 @@
 //                      mirrored about the first / last sample (section "order 3, mode 'constant'" below)
 //   outputs            float32: cast; uint16: floor(t+0.5) clamped to [0, 65535].
 // The coordinate grid (5 GB of float64 per FOV in the reference) is never materialised.
+// The arithmetic of these rules that more than one kernel needs (the prefilter of a line, tap weights, the 64-tap sum,
+// the output cast, the order of drift and field) is stated once, in ia3_spline.h.
 // Compiled with -ffp-contract=off.  HBM-bound streaming passes + an L2-served 64-tap gather.
 #include "ia3_rt.h"
 #include <math.h>
@@ -22,8 +24,8 @@
 
 using namespace ia3rt;
 
-#include "warp_iir0_kernel.inc"
-using namespace ia3warpk;
+#include "ia3_spline.h"
+using namespace ia3spline;
 
 namespace {
 
@@ -33,27 +35,6 @@ namespace {
 #else
 #define IA3_WARP_DEPTHS(X) X(25) X(30) X(33) X(35) X(40) X(45) X(50) X(60)
 #endif
-#define IA3_POLE3 (-0.26794919243112270647)
-
-template <class T> __device__ __forceinline__ T out_cvt(double t);
-template <> __device__ __forceinline__ float out_cvt<float>(double t) { return (float)t; }
-template <> __device__ __forceinline__ uint16_t out_cvt<uint16_t>(double t) {
-  t = t > 0 ? t + 0.5 : 0.0;
-  t = t > 65535.0 ? 65535.0 : t;
-  return (uint16_t)(int)t;
-}
-
-
-// x / 6.0, correctly rounded, without the division sequence (15-20 dependent instructions, nine of them per voxel in
-// the cubic weights): q = RN(x * RN(1/6)) is within an ulp of the quotient, the remainder r = x - 6q is exact in one
-// fused multiply-add, and RN(q + r * RN(1/6)) is then the correctly rounded quotient (Markstein's theorem; the weights
-// are far from the overflow / underflow ranges where it needs help).
-__device__ __forceinline__ double div6(double x) {
-  const double y = 0x1.5555555555555p-3;
-  const double q = x * y;
-  const double r = __builtin_fma(-6.0, q, x);
-  return __builtin_fma(r, y, q);
-}
 
 // P[z,x,y] = im[clamp(z-12), clamp(x-12), clamp(y-12)] as float64 (np.pad(mode='edge'))
 template <class T>
@@ -66,23 +47,6 @@ __global__ void spline_pad_k(const T* __restrict__ im, int Z, int X, int Y, doub
   P[((size_t)z * Xp + x) * Yp + y] = (double)im[((size_t)sz * X + sx) * Y + sy];
 }
 
-// start-of-line value of the causal recursion for the 'nearest'/'reflect' boundary (see header)
-// The sum runs over the whole line in SciPy.  When z^n underflows to zero (n >= 566) the mirror terms vanish exactly and
-// the sum is cut where the rest provably cannot change it: every remaining term is at most |z|^i * bound in magnitude
-// (bound = gain * largest |sample| the pass can meet), and an addend below a quarter ulp of the running sum leaves it
-// unchanged under round-to-nearest, so once |sum| * 2^-55 > |z|^i * bound all further additions are no-ops.  The test
-// is made after 64 terms and every 64 terms from there; a line whose leading samples are zero simply reads on.  The
-// largest sample is 65535 for uint16 sources and is measured for float32 ones (absmax_f32_k); each pass of the
-// prefilter can raise it by at most a factor 3 (the absolute sum of its impulse response).
-
-__device__ __forceinline__ double iir_bound(const IirInit& q) {
-  return q.amax_bits ? q.bound * (double)__uint_as_float(*q.amax_bits) : q.bound;
-}
-// true when no later term of the start sum can change `s` (see IirInit); NaN / inf bounds never pass
-__device__ __forceinline__ bool iir_sum_settled(double s, double zi, double bound) {
-  return fabs(s) * 0x1p-55 > fabs(zi) * bound || (zi == 0.0 && bound < INFINITY);
-}
-
 // bits of max |im| over a float32 stack: |x| as an unsigned integer orders finite < inf < NaN
 __global__ __launch_bounds__(256) void absmax_f32_k(const float* __restrict__ im, size_t n, unsigned* __restrict__ out) {
   unsigned m = 0;
@@ -93,84 +57,6 @@ __global__ __launch_bounds__(256) void absmax_f32_k(const float* __restrict__ im
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) { const unsigned v = (unsigned)__shfl_xor((int)m, o); m = v > m ? v : m; }
   if ((threadIdx.x & 63) == 0 && m > __hip_atomic_load(out, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(out, m);
-}
-
-// start value of the causal recursion of a strided line (element i at c + i*stride), see IirInit
-__device__ __forceinline__ double iir_start_strided(const double* __restrict__ c, size_t stride, int n, const IirInit& q) {
-  const double z = q.z, g = q.gain;
-  const double c0 = c[0] * g;
-  double s;
-  if (q.full) {
-    s = c0 + q.zn * (c[(size_t)(n - 1) * stride] * g);
-    double zi = z;
-    for (int i = 1; i < n; ++i) {
-      s += zi * (c[(size_t)i * stride] * g + q.zn * (c[(size_t)(n - 1 - i) * stride] * g));
-      zi *= z;
-    }
-  } else {
-    const double bound = iir_bound(q);
-    s = c0;
-    double zi = z;
-    for (int i = 1; i < n;) {
-      const int e = i + 63 < n ? i + 63 : n;
-      for (; i < e; ++i) { s += zi * (c[(size_t)i * stride] * g); zi *= z; }
-      if (iir_sum_settled(s, zi, bound)) break;
-    }
-  }
-  s *= q.scale;
-  s += c0;
-  return s;
-}
-
-// Two sweeps over a strided line, in place, from sample `from` (whose causal value `first` is known) to the end and
-// back: [from, n) holds raw samples on entry and coefficients on exit.
-// The recursions are serial in `prev`, their loads are not: eight samples are fetched ahead of the eight dependent
-// updates, so a thread keeps eight loads in flight instead of one (the kernel ran at 1.6 TB/s, latency-bound).
-// MIRROR: the anticausal start of the whole-sample-symmetric boundary (mode 'constant', below) instead of the
-// half-sample-symmetric one; needs the causal values of the last TWO samples (from <= n - 2).
-template <bool MIRROR = false>
-__device__ __forceinline__ void iir_two_sweeps_strided(double* __restrict__ c, size_t stride, int from, int n, double first,
-                                                       double z, double g) {
-  constexpr int B = 8;   // 16 in flight: no faster (2.36 against 2.25 ms)
-  double prev = first;
-  c[(size_t)from * stride] = prev;
-  int i = from + 1;
-  for (; i + B <= n; i += B) {
-    double in[B];
-#pragma unroll
-    for (int k = 0; k < B; ++k) in[k] = c[(size_t)(i + k) * stride];
-#pragma unroll
-    for (int k = 0; k < B; ++k) {
-      const double v = in[k] * g + z * prev;
-      c[(size_t)(i + k) * stride] = v;
-      prev = v;
-    }
-  }
-  for (; i < n; ++i) {
-    double v = c[(size_t)i * stride] * g + z * prev;
-    c[(size_t)i * stride] = v;
-    prev = v;
-  }
-  if (MIRROR) prev = ((z * c[(size_t)(n - 2) * stride] + prev) * z) / (z * z - 1.0);   // (c[n-2]: this thread's own store)
-  else prev = prev * (z / (z - 1.0));
-  c[(size_t)(n - 1) * stride] = prev;
-  i = n - 2;
-  for (; i - (B - 1) >= from; i -= B) {
-    double in[B];
-#pragma unroll
-    for (int k = 0; k < B; ++k) in[k] = c[(size_t)(i - k) * stride];
-#pragma unroll
-    for (int k = 0; k < B; ++k) {
-      const double v = z * (prev - in[k]);
-      c[(size_t)(i - k) * stride] = v;
-      prev = v;
-    }
-  }
-  for (; i >= from; --i) {
-    double v = z * (prev - c[(size_t)i * stride]);
-    c[(size_t)i * stride] = v;
-    prev = v;
-  }
 }
 
 // IIR along a strided axis: line p (lane along the contiguous axis), element i at base + i*stride
@@ -703,13 +589,8 @@ __global__ __launch_bounds__(256) void warp_cubic_mirror_k(const double* __restr
   const int x = blockIdx.y, zq = blockIdx.z;
   const size_t o = ((size_t)zq * X + x) * Y + y, V = (size_t)Z * X * Y;
   double cc[3] = {(double)zq, (double)x, (double)y};
-  if (fdt & 16) {
-    cc[0] = cc[0] - dz; cc[1] = cc[1] - dx; cc[2] = cc[2] - dy;
-    if (field) { cc[0] = cc[0] + field_at(field, fdt & 3, o); cc[1] = cc[1] + field_at(field, fdt & 3, V + o); cc[2] = cc[2] + field_at(field, fdt & 3, 2 * V + o); }
-  } else {
-    if (field) { cc[0] = cc[0] + field_at(field, fdt & 3, o); cc[1] = cc[1] + field_at(field, fdt & 3, V + o); cc[2] = cc[2] + field_at(field, fdt & 3, 2 * V + o); }
-    cc[0] = cc[0] - dz; cc[1] = cc[1] - dx; cc[2] = cc[2] - dy;
-  }
+  const double dr[3] = {dz, dx, dy};
+  warp_coord(cc, dr, field, fdt, [&](int a) { return field_at(field, fdt & 3, (size_t)a * V + o); });
   const int dims[3] = {Z, X, Y};
   bool outside = false;
 #pragma unroll
@@ -720,29 +601,12 @@ __global__ __launch_bounds__(256) void warp_cubic_mirror_k(const double* __restr
   for (int a = 0; a < 3; ++a) {
     const double c = cc[a];
     const double fl = floor(c);
-    const double yv = c - fl, zv = 1.0 - yv;
-    w[a][1] = div6(yv * yv * (yv - 2.0) * 3.0 + 4.0);
-    w[a][2] = div6(zv * zv * (zv - 2.0) * 3.0 + 4.0);
-    w[a][0] = div6(zv * zv * zv);
-    w[a][3] = 1.0 - w[a][0] - w[a][1] - w[a][2];
+    cubic_weights(c - fl, w[a]);
     const int st = (int)fl - 1;   // 0 <= fl <= n - 1 here
 #pragma unroll
     for (int k = 0; k < 4; ++k) idx[a][k] = mirror_idx(st + k, dims[a]);
   }
-  double t = 0.0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const double* row = C + ((size_t)idx[0][i] * X + idx[1][j]) * Y;
-#pragma unroll
-      for (int k = 0; k < 4; ++k) {
-        double c = row[idx[2][k]];
-        c = c * w[0][i]; c = c * w[1][j]; c = c * w[2][k];
-        t = t + c;
-      }
-    }
-  out[o] = out_cvt<T>(t);
+  out[o] = out_cvt<T>(gather64([&](int i0, int i1) { return C + ((size_t)i0 * X + i1) * Y; }, idx, w));
 }
 
 // orders 0 and 1 on the raw stack
@@ -755,13 +619,8 @@ __global__ __launch_bounds__(256) void warp_lin_k(const T* __restrict__ im, int 
   const int x = blockIdx.y, zq = blockIdx.z;
   const size_t o = ((size_t)zq * X + x) * Y + y, V = (size_t)Z * X * Y;
   double cc[3] = {(double)zq, (double)x, (double)y};
-  if (fdt & 16) {   // (grid - drift) + field: the order of classes/preprocess.py:923-935
-    cc[0] = cc[0] - dz; cc[1] = cc[1] - dx; cc[2] = cc[2] - dy;
-    if (field) { cc[0] = cc[0] + field_at(field, fdt & 3, o); cc[1] = cc[1] + field_at(field, fdt & 3, V + o); cc[2] = cc[2] + field_at(field, fdt & 3, 2 * V + o); }
-  } else {          // (grid + field) - drift: translate.py:19-25, io_tools/load.py:443-448
-    if (field) { cc[0] = cc[0] + field_at(field, fdt & 3, o); cc[1] = cc[1] + field_at(field, fdt & 3, V + o); cc[2] = cc[2] + field_at(field, fdt & 3, 2 * V + o); }
-    cc[0] = cc[0] - dz; cc[1] = cc[1] - dx; cc[2] = cc[2] - dy;
-  }
+  const double dr[3] = {dz, dx, dy};
+  warp_coord(cc, dr, field, fdt, [&](int a) { return field_at(field, fdt & 3, (size_t)a * V + o); });
   const int dims[3] = {Z, X, Y};
   if (mode == IA3_MODE_CONSTANT) {
     bool outside = false;
@@ -813,26 +672,16 @@ __global__ __launch_bounds__(256) void warp_cubic_k(const double* __restrict__ C
   const int Zp = Z + 2 * NPAD, Xp = X + 2 * NPAD, Yp = Y + 2 * NPAD;
   const size_t o = ((size_t)zq * X + x) * Y + y, V = (size_t)Z * X * Y;
   double cc[3] = {(double)zq, (double)x, (double)y};
-  if (fdt & 16) {   // (grid - drift) + field: the order of classes/preprocess.py:923-935
-    cc[0] = cc[0] - dz; cc[1] = cc[1] - dx; cc[2] = cc[2] - dy;
-    if (field) { cc[0] = cc[0] + field_at(field, fdt & 3, o); cc[1] = cc[1] + field_at(field, fdt & 3, V + o); cc[2] = cc[2] + field_at(field, fdt & 3, 2 * V + o); }
-  } else {          // (grid + field) - drift: translate.py:19-25, io_tools/load.py:443-448
-    if (field) { cc[0] = cc[0] + field_at(field, fdt & 3, o); cc[1] = cc[1] + field_at(field, fdt & 3, V + o); cc[2] = cc[2] + field_at(field, fdt & 3, 2 * V + o); }
-    cc[0] = cc[0] - dz; cc[1] = cc[1] - dx; cc[2] = cc[2] - dy;
-  }
+  const double dr[3] = {dz, dx, dy};
+  warp_coord(cc, dr, field, fdt, [&](int a) { return field_at(field, fdt & 3, (size_t)a * V + o); });
   const int dims[3] = {Zp, Xp, Yp};
   int idx[3][4]; double w[3][4];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     const double c = cc[a] + (double)NPAD;
     const double fl = floor(c);
-    const double yv = c - fl, zv = 1.0 - yv;
-    w[a][1] = div6(yv * yv * (yv - 2.0) * 3.0 + 4.0);
-    w[a][2] = div6(zv * zv * (zv - 2.0) * 3.0 + 4.0);
-    w[a][0] = div6(zv * zv * zv);
-    w[a][3] = 1.0 - w[a][0] - w[a][1] - w[a][2];
-    double f2 = fl < -8.0 ? -8.0 : (fl > (double)dims[a] + 8.0 ? (double)dims[a] + 8.0 : fl);
-    const int st = (int)f2 - 1;
+    cubic_weights(c - fl, w[a]);
+    const int st = IA3_CUBIC_FIRST_TAP(fl, dims[a]);
 #pragma unroll
     for (int k = 0; k < 4; ++k) idx[a][k] = clampi(st + k, dims[a]);
   }
@@ -863,8 +712,7 @@ __global__ __launch_bounds__(256) void warp_cubic_k(const double* __restrict__ C
           const unsigned off = zo[i] + xo[j];
           const v4u lo = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off, 0, 0);
           const v4u hi = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 16u, 0, 0);
-          const double cv[4] = {__hiloint2double((int)lo.y, (int)lo.x), __hiloint2double((int)lo.w, (int)lo.z),
-                                __hiloint2double((int)hi.y, (int)hi.x), __hiloint2double((int)hi.w, (int)hi.z)};
+          const double cv[4] = {words2double(lo.x, lo.y), words2double(lo.z, lo.w), words2double(hi.x, hi.y), words2double(hi.z, hi.w)};
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             double c = cv[k];
@@ -884,25 +732,14 @@ __global__ __launch_bounds__(256) void warp_cubic_k(const double* __restrict__ C
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const v2u q = __builtin_amdgcn_raw_buffer_load_b64(rsrc, roff + yoff[k], 0, 0);
-            double c = __hiloint2double((int)q.y, (int)q.x);
+            double c = words2double(q.x, q.y);
             c = c * w[0][i]; c = c * w[1][j]; c = c * w[2][k];
             t = t + c;
           }
         }
     }
   } else {
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        const double* row = C + ((size_t)idx[0][i] * Xp + idx[1][j]) * Yp;
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-          double c = row[idx[2][k]];
-          c = c * w[0][i]; c = c * w[1][j]; c = c * w[2][k];
-          t = t + c;
-        }
-      }
+    t = gather64([&](int i0, int i1) { return C + ((size_t)i0 * Xp + i1) * Yp; }, idx, w);
   }
   out[o] = out_cvt<T>(t);
 }
@@ -968,17 +805,11 @@ __global__ __launch_bounds__(256, OCC) void warp_cubic4_k(const double* __restri
     double cc[3] = {(double)zq, (double)x, (double)(y0 + v)};
 #pragma unroll
     for (int a = 0; a < 3; ++a) {
-      if (fdt & 16) { cc[a] = cc[a] - dr[a]; if (field) cc[a] = cc[a] + f[a][v]; }   // (grid - drift) + field
-      else { if (field) cc[a] = cc[a] + f[a][v]; cc[a] = cc[a] - dr[a]; }            // (grid + field) - drift
+      IA3_WARP_COORD(cc[a], dr[a], field, fdt, f[a][v]);
       const double c = cc[a] + (double)NPAD;
       const double fl = floor(c);
-      const double yv = c - fl, zv = 1.0 - yv;
-      w[v][a][1] = div6(yv * yv * (yv - 2.0) * 3.0 + 4.0);
-      w[v][a][2] = div6(zv * zv * (zv - 2.0) * 3.0 + 4.0);
-      w[v][a][0] = div6(zv * zv * zv);
-      w[v][a][3] = 1.0 - w[v][a][0] - w[v][a][1] - w[v][a][2];
-      const double f2 = fl < -8.0 ? -8.0 : (fl > (double)dims[a] + 8.0 ? (double)dims[a] + 8.0 : fl);
-      st[v][a] = (int)f2 - 1;
+      cubic_weights(c - fl, w[v][a]);
+      st[v][a] = IA3_CUBIC_FIRST_TAP(fl, dims[a]);
     }
   }
   const __amdgpu_buffer_rsrc_t rsrc =
@@ -1004,11 +835,11 @@ __global__ __launch_bounds__(256, OCC) void warp_cubic4_k(const double* __restri
 #pragma unroll
         for (int m = 0; m + 1 < RUN; m += 2) {
           const v4u q = __builtin_amdgcn_raw_buffer_load_b128(rsrc, off + 8u * m, 0, 0);
-          r[m] = __hiloint2double((int)q.y, (int)q.x); r[m + 1] = __hiloint2double((int)q.w, (int)q.z);
+          r[m] = words2double(q.x, q.y); r[m + 1] = words2double(q.z, q.w);
         }
         {
           const v2u q = __builtin_amdgcn_raw_buffer_load_b64(rsrc, off + 8u * (RUN - 1), 0, 0);   // RUN is odd
-          r[RUN - 1] = __hiloint2double((int)q.y, (int)q.x);
+          r[RUN - 1] = words2double(q.x, q.y);
         }
 #pragma unroll
         for (int v = 0; v < NV; ++v)
@@ -1038,7 +869,7 @@ __global__ __launch_bounds__(256, OCC) void warp_cubic4_k(const double* __restri
 #pragma unroll
           for (int k = 0; k < 4; ++k) {
             const v2u q = __builtin_amdgcn_raw_buffer_load_b64(rsrc, roff + yoff[k], 0, 0);
-            double c = __hiloint2double((int)q.y, (int)q.x);
+            double c = words2double(q.x, q.y);
             c = c * wz; c = c * w[v][1][j]; c = c * w[v][2][k];
             tv = tv + c;
           }
@@ -1058,12 +889,7 @@ int g_warp_warm = 64;   // IA3_TUNE_WARP_ONEPASS
 
 // pass: 0, 1, 2 = how many passes of the prefilter the samples have been through; amax_bits: see IirInit
 IirInit make_init(int n, int pass, double src_max, const unsigned* amax_bits) {
-  IirInit q;
-  q.z = IA3_POLE3;
-  q.gain = (1.0 - q.z) * (1.0 - 1.0 / q.z);
-  q.zn = pow(q.z, (double)n);
-  q.scale = q.z / (1.0 - q.zn * q.zn);
-  q.full = q.zn != 0.0 ? 1 : 0;
+  IirInit q = iir_init(n);
   q.bound = 1.001 * q.gain * pow(3.0, (double)pass) * (amax_bits ? 1.0 : src_max);
   q.amax_bits = amax_bits;
   return q;
