@@ -11,6 +11,12 @@ The module's 2-D FFT aligners are here as well (:733-820, :422-424): ``blurnorm2
 offset convention (``[y, x] - im2.shape + 1``), its defaults and ``return_cor``, all on the device through
 the entries ``alignment_tools`` uses (fft_align.hip), and the small host helpers ``minmax``, ``translate``
 and ``closest_faster``.  ``plt_val=True`` (matplotlib figures) is not provided.
+
+The module's fast path is here too (fastfit.hip): ``normalzie_im`` (:94-98), ``get_seed_points_base_v2`` (:100-126),
+``gfit_fast`` (:433-490) and ``fast_fit_big_image`` (:496-558) — closed-form moment fits, one wavefront per seed, no LM
+and no refit sweeps.  The path is meant for float stacks: on uint16 the reference's ``weights = im_ - bk`` wraps
+(``weights < 0`` never holds, heights near 65535 come out), and that is reproduced as it is.  ``get_seed_points_base``
+(v1, pyfftw Gaussian), ``troubleshoot=True`` and ``plt_val=True`` are not provided.
 """
 import ctypes as C
 import numpy as np
@@ -72,6 +78,173 @@ def translate(im, trans):
     dst = tuple(slice(max(-k, 0), min(n, n - k)) for k, n in zip(t, im.shape))
     out[dst] = im[src]
     return out
+
+
+def _resident(im):
+    """(DeviceStack, owned) for an ndarray or a DeviceStack."""
+    if isinstance(im, L.DeviceStack):
+        return im, False
+    return L.DeviceStack.upload(im), True
+
+
+def _normalise_dev(stack, sz):
+    sz = int(sz)
+    if sz > L.BLUR_MAX_GB:
+        raise NotImplementedError("box size %d: boxes up to %d are supported" % (sz, L.BLUR_MAX_GB))
+    h = C.c_void_p()
+    L.check(L.lib().ia3_fastfit_normalize_dev(stack._h, sz, C.byref(h)))
+    return L.DeviceStack(h, stack.shape, np.float32)
+
+
+def normalzie_im(im, sz=20):
+    """External/Fitting_v4.py:94-98 — ``float32(im)`` minus its ``sz x sz`` box blur, plane by plane, on the device with
+    the rules of ``blurnorm2d`` (anchor ``sz // 2``, BORDER_REFLECT_101, float64 window sums; boxes up to 32).  An ndarray
+    gives an ndarray, a ``DeviceStack`` a new ``DeviceStack``."""
+    stack, owned = _resident(im)
+    try:
+        out = _normalise_dev(stack, sz)
+    finally:
+        if owned:
+            stack.free()
+    if owned:
+        with out:
+            return out.download()
+    return out
+
+
+def get_seed_points_base_v2(im_sm, gfilt_size=5, filt_size=3, th_seed=3., max_num=None):
+    """External/Fitting_v4.py:100-126 — local maxima of the box-normalised stack (``gfilt_size=0``: of the stack as it
+    is) above ``th_seed`` times its standard deviation, neighbours within ``int(filt_size/2)`` taken modulo the shape
+    (at most 3).  Returns ``(centers_zxyh, std_)``: a (4, N) array [z, x, y, h], brightest first (float64 for a float
+    stack, int64 for uint16), and ``np.std`` of the stack — float32 for a float32 stack (the device sums in float64 and
+    rounds, NumPy sums in float32: equal to float32 rounding), float64 for uint16."""
+    pix = int(filt_size / 2)
+    if pix > 3:
+        raise NotImplementedError("filt_size %s: neighbours within %d voxels, at most 3 are supported" % (filt_size, pix))
+    if int(gfilt_size) != gfilt_size or gfilt_size < 0:
+        raise ValueError("gfilt_size is a box size: a non-negative integer")
+    if int(gfilt_size) > L.BLUR_MAX_GB:
+        raise NotImplementedError("box size %d: boxes up to %d are supported" % (gfilt_size, L.BLUR_MAX_GB))
+    stack, owned = _resident(im_sm)
+    try:
+        is_f32 = int(gfilt_size) != 0 or stack.dtype == np.float32
+        strong64 = isinstance(th_seed, np.floating) and np.dtype(type(th_seed)).itemsize >= 8
+        cut = -1 if (max_num is None or max_num < 0) else int(max_num)
+        capacity, n, sd = 4096, C.c_int(0), C.c_double(0)
+        while True:
+            rows = np.empty((capacity, 4), dtype=np.float64)
+            rc = L.lib().ia3_fastfit_seeds_dev(stack._h, int(gfilt_size), 2 * pix, C.c_double(float(th_seed)),
+                                               0 if strong64 else 1, cut, L.dptr(rows), capacity, C.byref(n), C.byref(sd))
+            if rc == L.IA3_ECAPACITY and n.value > capacity:
+                capacity = n.value
+                continue
+            L.check(rc)
+            break
+    finally:
+        if owned:
+            stack.free()
+    centers_zxyh = np.ascontiguousarray(rows[:n.value].T)
+    if not is_f32:
+        centers_zxyh = centers_zxyh.astype(np.int64)
+    if max_num is not None and max_num < 0:
+        centers_zxyh = centers_zxyh[:, :max_num]
+    return centers_zxyh, (np.float32(sd.value) if is_f32 else np.float64(sd.value))
+
+
+def inv_sigma(sigma):
+    """External/Fitting_v4.py:426-432 — inverse of a symmetric 3 x 3 matrix by cofactors."""
+    [[a, d, e], [d, b, f], [e, f, c]] = sigma
+    det = a * b * c - c * d ** 2 - b * e ** 2 + 2 * d * e * f - a * f ** 2
+    return np.array([[(b * c - f ** 2) / det, (-(c * d) + e * f) / det, (-(b * e) + d * f) / det],
+                     [(-(c * d) + e * f) / det, (a * c - e ** 2) / det, (d * e - a * f) / det],
+                     [(-(b * e) + d * f) / det, (d * e - a * f) / det, (a * b - d ** 2) / det]])
+
+
+_FAST_KINDS = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.float64): 2}
+
+
+def gfit_fast(im_, X_, bk_f=0.1, reconstruct=False, plt_val=False, compare_with_fitting=False):
+    """External/Fitting_v4.py:433-490 — closed-form moment fit of one voxel set on the device: ``[h, z, x, y, bk, a, b, c,
+    d, e, f, eps]`` as float64 (order-statistic background, height, weighted centroid, weighted covariance).  ``im_``:
+    (n,) float32, float64 or uint16 values, n <= 512; ``X_``: (3, n) integer coordinates.  ``reconstruct=True`` evaluates
+    ``inv_sigma``, the model and ``eps`` on the host from the device's numbers; otherwise ``eps`` is NaN."""
+    if plt_val:
+        raise NotImplementedError("plt_val=True (matplotlib figures) is not provided")
+    im_ = np.asarray(im_)
+    if len(im_) == 0:
+        return np.array([np.nan] * 12)
+    if im_.dtype not in _FAST_KINDS:
+        raise TypeError("gfit_fast takes float32, float64 or uint16 values, got %s" % im_.dtype)
+    X = np.asarray(X_)
+    if X.shape != (3, len(im_)) or X.dtype.kind not in "iu":
+        raise ValueError("X_ should be a (3, n) integer array")
+    vals = np.ascontiguousarray(im_, dtype=np.float64)
+    coords = np.ascontiguousarray(X.T, dtype=np.int32)
+    out = np.empty(12, dtype=np.float64)
+    L.check(L.lib().ia3_fastfit_voxels(L.dptr(vals), L.ptr(coords), len(vals), _FAST_KINDS[im_.dtype],
+                                       C.c_double(float(bk_f)), L.dptr(out)))
+    if reconstruct:
+        h, bk = out[0], out[4]
+        a, b, c, d, e, f = out[5:11]
+        X_c = X.T - out[1:4]
+        iCov = inv_sigma([[a, d, e], [d, b, f], [e, f, c]])
+        im_fit = h * np.exp(-np.sum(np.dot(X_c, iCov) * X_c, -1) * 0.5) + bk
+        out[11] = np.mean(np.abs(im_ - im_fit))
+    return out
+
+
+def fast_fit_big_image(im, centers_zxy, radius_fit=4, avoid_neigbors=True, recenter=False, verbose=True,
+                       better_fit=False, troubleshoot=False):
+    """External/Fitting_v4.py:496-558 — ``gfit_fast`` for every centre on the integer ball of ``radius_fit`` (offsets in
+    ``[-r, r)``, 254 voxels for 4; at most 5), clipped to the image: (N, 12) float64 rows, shape (0,) for no centres.
+    ``avoid_neigbors``: each ball keeps the offsets nearer to its centre than to any other centre within ``2 r`` (ties to
+    the lowest index); ``recenter``: the ball moves to its first maximum; ``better_fit``: the LM fit
+    ``GaussianFit(delta_center=2.5)`` on the same voxels instead, (N, 11) float32 rows.  ``verbose`` prints nothing.
+    ``im``: ndarray or ``DeviceStack``."""
+    if troubleshoot:
+        raise NotImplementedError("troubleshoot=True (matplotlib figures) is not provided")
+    if len(centers_zxy) == 0:
+        return np.array([])
+    cen = np.ascontiguousarray(centers_zxy, dtype=np.float64)
+    if cen.ndim != 2 or cen.shape[1] != 3:
+        raise ValueError("centers_zxy should be an (N, 3) array")
+    r = int(radius_fit)
+    n = len(cen)
+    g = np.arange(-r, r)
+    nball = int(np.count_nonzero(np.add.outer(np.add.outer(g * g, g * g), g * g) <= r * r))
+    if nball > 512:
+        raise NotImplementedError("radius_fit %d: balls of up to 512 voxels (radius_fit <= 5) are supported" % r)
+    stack, owned = _resident(im)
+    try:
+        out = np.empty((n, 12), dtype=np.float64)
+        if better_fit:
+            cnt = np.empty(n, dtype=np.int32)
+            vals = np.empty((n, nball), dtype=np.float64)
+            zxy = np.empty((n, nball, 3), dtype=np.int32)
+            extra = (L.ptr(cnt), L.dptr(vals), L.ptr(zxy))
+        else:
+            extra = (None, None, None)
+        L.check(L.lib().ia3_fastfit_moments_dev(stack._h, L.dptr(cen), n, r, 1 if avoid_neigbors else 0,
+                                                1 if recenter else 0, C.c_double(0.1), L.dptr(out), *extra))
+        dtype = stack.dtype
+    finally:
+        if owned:
+            stack.free()
+    if not better_fit:
+        return out
+    ps = np.full((n, 11), np.nan, dtype=np.float32)
+    rows = [i for i in range(n) if cnt[i] > 0]
+    ims = [vals[i, :cnt[i]].astype(dtype) for i in rows]
+    Xs = [zxy[i, :cnt[i]].T for i in rows]
+    starts = [X[:, np.argmax(v)] for v, X in zip(ims, Xs)]       # the voxel of the ball's first maximum
+    big = [k for k, v in enumerate(ims) if len(v) >= 10]         # GaussianFit.fit leaves fewer voxels unfitted (:382-383)
+    if big:
+        fitted = gaussfit_batch([ims[k] for k in big], [Xs[k] for k in big], [starts[k] for k in big], delta_center=2.5)[0]
+        for k, row in zip(big, fitted):
+            ps[rows[k]] = row
+    for k in set(range(len(rows))) - set(big):
+        ps[rows[k]] = GaussianFit(ims[k], Xs[k], center=starts[k], delta_center=2.5).p
+    return ps
 
 
 def gaussfit_batch(ims, Xs, centers, delta_center=3., min_w=0.5, max_w=4., init_w=1.5):

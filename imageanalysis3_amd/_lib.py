@@ -14,6 +14,7 @@ IA3_U16, IA3_F32 = 0, 1
 IA3_OK, IA3_EINVAL, IA3_EHIP, IA3_ENOMEM, IA3_ECAPACITY, IA3_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
 MODE_REFLECT, MODE_NEAREST, MODE_CONSTANT = 0, 1, 2
 BLUR_DIVIDE, BLUR_SUBTRACT = 0, 1                   # ia3_blurnorm2d modes
+BLUR_MAX_GB = 32                                    # IA3_BLUR_MAX_GB
 OFFSET_ALIGNMENT_TOOLS, OFFSET_FITTING_V4 = 0, 1    # fftalign_2d offset conventions
 
 EXPORTS = [
@@ -38,6 +39,7 @@ EXPORTS = [
     "ia3_stack_order_stats_dev", "ia3_stack_percentiles_dev", "ia3_clip_sum_z_dev",
     "ia3_gaussian_filter2d_f64_dev", "ia3_gaussian_filter2d_f64", "ia3_illumination_image_profile_dev",
     "ia3_crop_pairs_dev", "ia3_poly_field_dev", "ia3_buffer_alloc", "ia3_buffer_download", "ia3_bleedthrough_profile_dev",
+    "ia3_fastfit_normalize_dev", "ia3_fastfit_seeds_dev", "ia3_fastfit_moments_dev", "ia3_fastfit_voxels",
 ]
 
 

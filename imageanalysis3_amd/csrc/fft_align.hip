@@ -723,6 +723,21 @@ int g_fft_c2c = 0;   // IA3_TUNE_FFT_C2C: 1 = complex transforms of the real sta
 
 namespace ia3k { void set_dft_valu(int on) { g_dft_valu = on != 0; } void set_fft_c2c(int on) { g_fft_c2c = on != 0; } }
 
+namespace ia3k {
+// every z plane of a resident stack through blurnorm_k (float32 out): normalzie_im of External/Fitting_v4.py:94-98
+int blurnorm_planes(const void* im, int dtype, int Z, int X, int Y, int gb, int mode, float* out) {
+  if (gb < 1 || gb > BLUR_MAX_GB) return set_error(IA3_EUNSUPPORTED, "box size %d outside the supported range 1..%d", gb, BLUR_MAX_GB);
+  hipStream_t st = stream();
+  const size_t plane = (size_t)X * Y;
+  for (int z = 0; z < Z; ++z) {
+    if (dtype == IA3_U16) launch_blurnorm((const uint16_t*)im + z * plane, X, Y, gb, mode, out + z * plane, st);
+    else launch_blurnorm((const float*)im + z * plane, X, Y, gb, mode, out + z * plane, st);
+  }
+  IA3_KCHECK();
+  return IA3_OK;
+}
+}  // namespace ia3k
+
 extern "C" {
 
 int ia3_fftalign_2d(const double* im1, int s1x, int s1y, const double* im2, int s2x, int s2y,

@@ -1633,6 +1633,7 @@ int ia3_fit_create(const ia3_stack* im, const double* centers_zxy, int n, const 
 
 namespace ia3k {
 void set_fit_nblist(int cap) { g_nb_cap = cap < 0 ? 0 : (cap > MAXNB ? MAXNB : cap); }
+int get_fit_nblist() { return g_nb_cap; }   // fastfit.hip reads its neighbour lists under the same knob
 void set_fit_fuse(int on) { g_fit_fuse = on ? 1 : 0; }
 void set_fit_maxfev(int n) { g_fit_maxfev = n; }
 void set_fit_waves(int n) { g_fit_waves = n < 1 ? 1 : (n > IA3_FIT_LB ? IA3_FIT_LB : n); }

@@ -1,21 +1,19 @@
 // Start point of GaussianFit (External/Fitting_v4.py:175-185): log of the mean of the 10 smallest
 // / 10 largest voxel values, offsets 0, widths init_w, angles 0 — every entry rounded to float32
 // (the reference builds p_ as a float32 array).  The means reproduce NumPy's summation order
-// for a contiguous 10-vector (8-lane pairwise block + 2 tail adds) in the dtype NumPy would use:
+// for a contiguous 10-vector (ia3_npsum.h: 8-lane pairwise block + 2 tail adds) in the dtype NumPy would use:
 //   kind 0: float32 data  -> float32 accumulation, float32 division
 //   kind 1: integer data  -> exact float64
 //   kind 2: float64 data  -> float64 pairwise
 #pragma once
 #include "ia3_model.h"
+#include "ia3_npsum.h"
 
 namespace ia3 {
 
 template <class T>
 IA3_HD T np_sum10(const T* a) {
-  T r = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-  r = r + a[8];
-  r = r + a[9];
-  return r;
+  return np_sum<T>(a, 10);
 }
 
 // lo10 / hi10: the ten smallest / largest values, each ascending.

@@ -185,4 +185,7 @@ int drift_crops(const ia3_stack* src, DriftRef* ref, int first, int count, int u
 // fits run / model evaluations / voxel evaluations / shader cycles in dependency waits / wave cycles of a fitter, as of its
 // last ia3_fit_results(_ex)
 void fit_host_counters(const ia3_fitter* f, long long out[5]);
+int get_fit_nblist();   // IA3_TUNE_FIT_NBLIST as set (fit.hip)
+// every z plane of a device stack minus (mode 1) / over (mode 0) its gb x gb box blur, float32 out (fft_align.hip)
+int blurnorm_planes(const void* im, int dtype, int Z, int X, int Y, int gb, int mode, float* out);
 }  // namespace ia3k

@@ -502,6 +502,34 @@ void ia3_drift_ref_free(ia3_drift_ref* r);
 int ia3_align_image_ref(const ia3_stack* src, ia3_drift_ref* ref, int upsample, int normalization, int min_good_drifts,
                         double drift_diff_th, double* drift, int* flag, double* drifts_out, int* n_used);
 
+/* ---- External/Fitting_v4.py fast path: box-normalised seeds and closed-form moment fits ---------------------------
+ * normalzie_im (:94-98): new resident float32 stack = float32(im) minus its sz x sz box blur, plane by plane, with the
+ * arithmetic of ia3_blurnorm2d (anchor sz / 2, BORDER_REFLECT_101, float64 window sums); 1 <= sz <= IA3_BLUR_MAX_GB,
+ * larger boxes are IA3_EUNSUPPORTED. */
+int ia3_fastfit_normalize_dev(const ia3_stack* im, int sz, ia3_stack** out);
+/* get_seed_points_base_v2 (:100-126).  gfilt_size 0: the stack as it is, in its own dtype; otherwise its normalzie_im.
+ * std_out = np.std of that stack, computed in float64 by fixed-order reductions and rounded to float32 for a float32
+ * stack (NumPy sums in float32 there: the two agree to float32 rounding, not bit for bit).  Kept voxels: v > std * th_seed
+ * (the product in float32 when th_f32 != 0 and the stack is float32: a Python number; else float64), v > 0 and v >= every
+ * neighbour within filt_size / 2 on each axis, neighbours taken modulo the shape (filt_size / 2 <= 3).  zxyh: rows
+ * [z, x, y, h], brightest first (equal heights: descending voxel order), at most max_num (< 0: all); *n_out their number;
+ * IA3_ECAPACITY when it exceeds `capacity` rows. */
+int ia3_fastfit_seeds_dev(const ia3_stack* im, int gfilt_size, int filt_size, double th_seed, int th_f32, int max_num,
+                          double* zxyh, int capacity, int* n_out, double* std_out);
+/* fast_fit_big_image (:496-558) with gfit_fast (:433-458) for every centre: out12 = n x 12 float64 rows [h, z, x, y, bk,
+ * a, b, c, d, e, f, eps] (eps NaN; a row of NaN for a centre whose ball has no voxel in the image).  The ball: offsets
+ * in [-radius_fit, radius_fit) with d^2 <= radius_fit^2 (radius_fit <= 5), at int(centre) + offset, clipped to the image;
+ * avoid_neighbors: only the offsets nearer to this centre than to any other centre within 2 radius_fit (cdist's float64
+ * arithmetic, ties to the lowest index); recenter: the ball is moved to its first maximum, the same offsets applied there.
+ * uint16 stacks: the weights wrap as NumPy's uint16 subtraction does.  Optional (all three or none): vox_count[n] and the
+ * voxel list each centre was fitted on, nball slots per centre (nball = number of ball offsets): vox_vals n x nball,
+ * vox_zxy n x nball x 3. */
+int ia3_fastfit_moments_dev(const ia3_stack* im, const double* centers_zxy, int n, int radius_fit, int avoid_neighbors,
+                            int recenter, double bk_f, double* out12, int* vox_count, double* vox_vals, int* vox_zxy);
+/* gfit_fast on one explicit voxel list (n <= 512): vals n float64 copies of the values, coords_zxy n x 3, kind the dtype
+ * whose arithmetic the weights follow (0 float32, 1 uint16, 2 float64).  n = 0: twelve NaN. */
+int ia3_fastfit_voxels(const double* vals, const int* coords_zxy, int n, int kind, double bk_f, double* out12);
+
 /* ---- warp -------------------------------------------------------------------------------------
  * correction_tools/translate.py:5-31 warp_3d_image and its inlined twins (io_tools/load.py:438-453,
  * classes/preprocess.py:918-946): out = map_coordinates(im, grid (+ field) - drift, order, mode, cval).

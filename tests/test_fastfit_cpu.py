@@ -1,0 +1,175 @@
+"""CPU: the Fitting_v4 fast path without a device — the names and signatures, NumPy's summation order as the library
+states it (csrc/ia3_npsum.h, built for the host by tests/native/fastfit_cpu.cpp) against np.sum bit for bit, the moment
+fit's arithmetic (csrc/ia3_fastfit.h) and the NumPy statement tests/harness/fastfit_ref.py against the reference's own
+rows (tests/golden/fastfit.npz, written by scripts/make_fastfit_golden.py)."""
+import ctypes as C
+import inspect
+import json
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from conftest import load_golden
+from harness import fastfit_ref as FR
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SO = os.path.join(HERE, "native", "libfastfitcpu.so")
+E = inspect.Parameter.empty
+
+SIGNATURES = {
+    "normalzie_im": [("im", E), ("sz", 20)],
+    "get_seed_points_base_v2": [("im_sm", E), ("gfilt_size", 5), ("filt_size", 3), ("th_seed", 3.), ("max_num", None)],
+    "gfit_fast": [("im_", E), ("X_", E), ("bk_f", 0.1), ("reconstruct", False), ("plt_val", False),
+                  ("compare_with_fitting", False)],
+    "fast_fit_big_image": [("im", E), ("centers_zxy", E), ("radius_fit", 4), ("avoid_neigbors", True), ("recenter", False),
+                           ("verbose", True), ("better_fit", False), ("troubleshoot", False)],
+    "inv_sigma": [("sigma", E)],
+}
+
+
+@pytest.fixture(scope="module")
+def native():
+    src = os.path.join(HERE, "native", "fastfit_cpu.cpp")
+    dep = os.path.join(HERE, "..", "imageanalysis3_amd", "csrc")
+    newest = max(os.path.getmtime(p) for p in (src, os.path.join(dep, "ia3_fastfit.h"), os.path.join(dep, "ia3_npsum.h")))
+    if not os.path.isfile(SO) or os.path.getmtime(SO) < newest:
+        subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", SO, src])
+    lib = C.CDLL(SO)
+    lib.ia3cpu_npsum_f32.restype = C.c_float
+    lib.ia3cpu_npsum_f64.restype = C.c_double
+    return lib
+
+
+@pytest.fixture(scope="module")
+def gold():
+    return load_golden("fastfit.npz")
+
+
+def _same(a, b):
+    a, b = np.asarray(a), np.asarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def test_names_and_signatures():
+    from imageanalysis3_amd.External import Fitting_v4 as F4
+    for name, want in SIGNATURES.items():
+        params = inspect.signature(getattr(F4, name)).parameters.values()
+        assert [(p.name, p.default) for p in params] == want, name
+        assert all(p.kind == p.POSITIONAL_OR_KEYWORD for p in params)
+
+
+def test_refusals_and_empty_inputs_before_the_device():
+    from imageanalysis3_amd.External.Fitting_v4 import (fast_fit_big_image, gfit_fast, get_seed_points_base_v2,
+                                                        normalzie_im)
+    im = np.zeros((4, 8, 8), np.float32)
+    with pytest.raises(NotImplementedError):
+        fast_fit_big_image(im, [[1, 1, 1]], troubleshoot=True)
+    with pytest.raises(NotImplementedError):
+        gfit_fast(np.ones(4, np.float32), np.zeros((3, 4), int), plt_val=True)
+    with pytest.raises(NotImplementedError):
+        get_seed_points_base_v2(im, filt_size=9)
+    with pytest.raises(NotImplementedError):
+        get_seed_points_base_v2(im, gfilt_size=33)
+    with pytest.raises(NotImplementedError):
+        fast_fit_big_image(im, [[1, 1, 1]], radius_fit=6)
+    assert fast_fit_big_image(im, []).shape == (0,)
+    empty = gfit_fast(np.zeros(0, np.float32), np.zeros((3, 0), int))
+    assert empty.shape == (12,) and empty.dtype == np.float64 and np.isnan(empty).all()
+
+
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_summation_header_equals_numpy_for_every_length(native, dtype):
+    """np.sum (1-D) and np.add.reduce over the contiguous last axis of a 2-D array, every n from 1 to 512."""
+    rng = np.random.default_rng(5)
+    fn = native.ia3cpu_npsum_f32 if dtype == np.float32 else native.ia3cpu_npsum_f64
+    for n in range(1, 513):
+        # magnitudes spread over six decades and both signs: a different association changes the last bits
+        a = (rng.standard_normal((3, n)) * 10.0 ** rng.uniform(-3, 3, (3, n))).astype(dtype)
+        want = np.add.reduce(a, -1)
+        for r in range(3):
+            row = np.ascontiguousarray(a[r])
+            got = dtype(fn(row.ctypes.data_as(C.c_void_p), n))
+            assert got.tobytes() == want[r].tobytes() == np.sum(row).tobytes(), (n, r)
+
+
+def _native_moments(native, vals, X, bk_f=0.1):
+    vals = np.asarray(vals)
+    kind = {np.dtype(np.float32): 0, np.dtype(np.uint16): 1, np.dtype(np.float64): 2}[vals.dtype]
+    v = np.ascontiguousarray(vals, dtype=np.float64)
+    x = np.ascontiguousarray(X, dtype=np.int32)
+    out = np.empty(12)
+    native.ia3cpu_ff_moments(v.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p), len(v), kind, C.c_double(bk_f),
+                             out.ctypes.data_as(C.c_void_p))
+    return out
+
+
+def test_gfit_fast_statement_and_header_equal_reference(native, gold):
+    vals, X = gold["gf_vals"], gold["gf_X"]
+    u16 = gold["c3_im"][3:7, 18:23, 20:24].ravel()
+    cases = [("gf_plain", vals, 0.1), ("gf_bk03", vals, 0.3), ("gf_f64", vals.astype(np.float64), 0.1), ("gf_u16", u16, 0.1)]
+    for key, v, bk_f in cases:
+        assert _same(FR.moments(v, X, bk_f), gold[key]), key
+        assert _same(_native_moments(native, v, X, bk_f), gold[key]), key
+    assert _same(gold["gf_recon"][:11], gold["gf_plain"][:11])
+
+
+def test_fast_fit_statement_and_header_equal_reference(native, gold):
+    """Every fit run of the fixture (NaN row, tie voxels, cut ball, uint16 wrap included): the NumPy statement and the
+    header's arithmetic on the statement's voxel sets, bit for bit in all twelve columns."""
+    meta = json.load(open(os.path.join(HERE, "golden", "fastfit.json")))
+    seen = 0
+    for key, kw in meta["fit_runs"].items():
+        kw = {k: v for k, v in kw.items() if k != "n"}
+        if kw.pop("better_fit", False):
+            continue
+        case = key.split("_")[0]
+        im, cen = gold[case + "_im"], gold[case + "_centres"]
+        assert _same(FR.fast_fit(im, cen, **kw), gold[key]), key
+        rows = np.array([_native_moments(native, v, x) for v, x in FR.voxel_sets(im, cen, **kw)])
+        assert _same(rows, gold[key]), key
+        seen += 1
+    assert seen >= 7
+    assert np.isnan(gold["c2_fit_default"][-1]).all()
+    assert gold["c3_fit_default"][:, 0].max() > 60000     # the uint16 wrap, as measured on the reference
+
+
+def test_voronoi_header_equals_statement(native, gold):
+    """ff_loses over the neighbour list against the statement's argmin of distances, on the fixture's tie pair and on
+    random integer and fractional fields."""
+    off = np.ascontiguousarray(FR.ball_offsets(4), dtype=np.int32)
+    assert len(off) == 254
+    rng = np.random.default_rng(9)
+    fields = [gold["c2_centres"], np.floor(rng.uniform(0, 14, (40, 3))), rng.uniform(0, 14, (40, 3))]
+    ties = 0
+    for cen in fields:
+        cen = np.ascontiguousarray(cen, dtype=np.float64)
+        for i in range(len(cen)):
+            diff = cen - cen[i]
+            near = np.nonzero(np.sqrt((diff * diff).sum(1)) <= 8)[0]
+            d = (cen[near] - cen[i])[:, None, :] - off[None].astype(np.float64)
+            dist = np.sqrt((d[..., 0] ** 2 + d[..., 1] ** 2) + d[..., 2] ** 2)
+            want = near[np.argmin(dist, 0)] == i
+            ties += int(np.sum(np.sum(dist == dist.min(0), 0) > 1))
+            js = np.ascontiguousarray(near[near != i], dtype=np.int32)
+            own = np.zeros(len(off), dtype=np.uint8)
+            native.ia3cpu_ff_owner(cen.ctypes.data_as(C.c_void_p), i, js.ctypes.data_as(C.c_void_p), len(js),
+                                   off.ctypes.data_as(C.c_void_p), len(off), own.ctypes.data_as(C.c_void_p))
+            assert np.array_equal(own.astype(bool), want), i
+    assert ties > 100
+
+
+def test_seed_statement_equals_reference(gold):
+    meta = json.load(open(os.path.join(HERE, "golden", "fastfit.json")))
+    for key, run in meta["seed_runs"].items():
+        case = key.split("_")[0]
+        got, std_ = FR.seeds(gold[case + "_im"], run["gfilt_size"], run["filt_size"], run["th_seed"], run["max_num"])
+        assert _same(got, gold[key]) and _same(std_, gold[key + "_std"]), key
+    for case in ("c1", "c2", "c3"):
+        assert _same(FR.normalise(gold[case + "_im"]), gold[case + "_norm20"])
+    # the wrap-around comparison decides a seed of case 1: (0, 0, 0) tops its in-image neighbourhood and is dropped
+    im, s = gold["c1_im"], gold["c1_seeds_g0_f3"]
+    assert im[0, 0, 0] == im[:2, :2, :2].max() and not np.any(np.all(s[:3] == 0, 0))
+    assert gold["c3_seeds_g0_f3"].dtype == np.int64 and gold["c3_seeds_g0_f3_std"].dtype == np.float64
+    assert gold["c1_seeds_g0_f3"].dtype == np.float64 and gold["c1_seeds_g0_f3_std"].dtype == np.float32
