@@ -2,9 +2,16 @@
 ``iter_fit_seed_points`` (:559-683) backed by the wave-per-ball LM kernels of libia3.so.
 
 The class keeps the reference's constructor, ``firstfit()`` / ``repeatfit()`` and the attributes
-callers read (``ps``, ``centers_fit``, ``success``, ``n_iter``, ``centers``).  The float64 residual
-stack ``im_subtr`` / ``im_add`` and the per-seed ``ims_rec`` arrays of the reference are internal
-state of its Gauss-Seidel loop; the device path never materialises them (fit.hip header).
+callers read: ``ps``, ``centers_fit``, ``success``, ``n_iter``, ``centers``, and the four views of a fit — ``gparms``
+(per seed ``[im_, X, center]`` of its first fit), ``ims_rec`` (per seed the fitted Gaussian over its ball, or NaN),
+``im_subtr`` and ``im_add`` (the float64 image minus the first-fit / the current reconstructions).  The device path
+never materialises the views while it fits (fit.hip header); they are rendered on first access by kernels of their own
+from the per-seed records the fit left behind, cached on the object, and dropped by the next ``firstfit()`` /
+``repeatfit()``.  ``im_add`` is defined per voxel as the image minus the reconstructions that cover it in ascending seed
+order, which the reference's in-place updates equal up to float64 rounding order.
+``residual_stack()`` gives the same residual as a float32 ``DeviceStack`` for a second seeding pass on the device.  The
+fitter handle stays alive for this until the object is deleted or ``release()`` is called; a ``DeviceStack`` passed as
+``im`` must stay alive as long (a view asked for after it was freed raises ``AttributeError``).
 
 The module's 2-D FFT aligners are here as well (:733-820, :422-424): ``blurnorm2d`` (the box blur is
 *subtracted* here, divided in ``alignment_tools``), ``fftalign_2d`` / ``fft3d_from2d`` with this module's
@@ -373,6 +380,21 @@ class GaussianFit():
         return self.f0
 
 
+def split_voxel_sets(counts, zxy, vals, centers, dtype):
+    """The reference's ``gparms`` from the packed buffers of ``ia3_fit_view_voxels``: per seed ``[im_, X, center]`` with
+    ``im_`` the first ``counts[i]`` values in the image's dtype, ``X`` their (3, nvox) int64 coordinates and ``center``
+    the seed as a list."""
+    dtype = np.dtype(dtype)
+    return [[vals[i, :k].astype(dtype), np.ascontiguousarray(zxy[i, :k].T, dtype=np.int64), [float(v) for v in centers[i]]]
+            for i, k in enumerate(int(c) for c in counts)]
+
+
+def split_reconstructions(counts, has_rec, recs):
+    """The reference's ``ims_rec`` from the packed buffers of ``ia3_fit_view_recs``: per seed a float64 array of
+    ``counts[i]`` values, or the scalar ``np.nan`` where no fit of the seed has succeeded."""
+    return [np.array(recs[i, :int(k)], dtype=np.float64) if h else np.nan for i, (k, h) in enumerate(zip(counts, has_rec))]
+
+
 class iter_fit_seed_points():
     def __init__(self, im, centers, radius_fit=5, min_delta_center=1., max_delta_center=2.5,
                  n_max_iter=10, max_dist_th=0.1,
@@ -400,6 +422,8 @@ class iter_fit_seed_points():
         self.init_w = init_w
         self._own_stack = None
         self._fitter = None
+        self._fitted = False      # firstfit() has run on at least one seed: the views exist
+        self.keep_views = True    # False before firstfit(): no first-fit snapshot is kept and the views are not offered
         self.ps = []
         self.success = []
         self.centers_fit = []
@@ -436,7 +460,9 @@ class iter_fit_seed_points():
         self.centers_fit = [ps[i, 1:4] for i in range(n)]
         self.nvox = nv
 
-    def _release(self):
+    def release(self):
+        """Give the fitter handle and the uploaded copy of a host image back.  ``ps``, ``success`` and every view
+        that has been read stay; a view that has not been rendered yet is gone."""
         if self._fitter is not None:
             L.lib().ia3_fit_destroy(self._fitter)
             self._fitter = None
@@ -446,16 +472,95 @@ class iter_fit_seed_points():
 
     def __del__(self):
         try:
-            self._release()
+            self.release()
         except Exception:
             pass
+
+    # -- views of the fit (External/Fitting_v4.py:597-598, :605, :623, :632-639, :674-675) ------------------------
+    _VIEWS = ("gparms", "ims_rec", "im_subtr", "im_add")
+
+    def _drop_views(self):
+        for name in self._VIEWS:
+            self.__dict__.pop(name, None)
+
+    def __getattr__(self, name):   # reached only for names the object does not hold
+        if name not in iter_fit_seed_points._VIEWS:
+            raise AttributeError("%r object has no attribute %r" % (type(self).__name__, name))
+        if not self.__dict__.get("_fitted"):   # before firstfit(), or no seeds: the reference has not made them either
+            raise AttributeError("%r object has no attribute %r (firstfit() has not fitted any seed)"
+                                 % (type(self).__name__, name))
+        if not self.keep_views:
+            raise AttributeError("%s was not kept: keep_views was False at firstfit()" % name)
+        if self._fitter is None:
+            raise AttributeError("%s was not rendered before the fitter was released (release())" % name)
+        self._check_stack()
+        value = getattr(self, "_render_" + name)()
+        self.__dict__[name] = value
+        return value
+
+    def _check_stack(self):
+        """A ``DeviceStack`` passed as ``im`` belongs to the caller and has to outlive the views: the kernels read it."""
+        if self._stack._h is None:
+            raise AttributeError("the DeviceStack this fitter reads has been freed: views are rendered from the image")
+
+    def _render_gparms(self):
+        n, nball = len(self.centers), len(self.zb)
+        cnt = np.empty(n, dtype=np.int32)
+        zxy = np.empty((n, nball, 3), dtype=np.int32)
+        vals = np.empty((n, nball), dtype=np.float64)
+        L.check(L.lib().ia3_fit_view_voxels(self._fitter, L.ptr(cnt), L.ptr(zxy), L.dptr(vals)))
+        return split_voxel_sets(cnt, zxy, vals, self.centers, self._stack.dtype)
+
+    def _records(self, which=1):
+        """(counts, has_rec, recs (n, nball), x11 (n, 11)) of the first-fit (0) or the current (1) records; the rows of
+        ``x11`` are the unconstrained parameters of ``GaussianFit.p_`` and the ``delta_center`` of that fit."""
+        n, nball = len(self.centers), len(self.zb)
+        cnt = np.empty(n, dtype=np.int32)
+        has = np.empty(n, dtype=np.uint8)
+        recs = np.empty((n, nball), dtype=np.float64)
+        x11 = np.empty((n, 11), dtype=np.float64)
+        L.check(L.lib().ia3_fit_view_recs(self._fitter, int(which), L.ptr(cnt), L.ptr(has), L.dptr(recs), L.dptr(x11)))
+        return cnt, has, recs, x11
+
+    def _render_ims_rec(self):
+        cnt, has, recs, _ = self._records(1)
+        return split_reconstructions(cnt, has, recs)
+
+    def _render_residual(self, which):
+        out = np.empty((self.sz, self.sx, self.sy), dtype=np.float64)
+        L.check(L.lib().ia3_fit_view_residual(self._fitter, which, L.dptr(out)))
+        return out
+
+    def _render_im_subtr(self):
+        return self._render_residual(0)
+
+    def _render_im_add(self):
+        return self._render_residual(1)
+
+    def residual_stack(self, which="add"):
+        """``im_subtr`` (``"subtr"``) or ``im_add`` (``"add"``) rounded once to float32, as a new ``DeviceStack``:
+        ``get_seeds`` / ``fit_fov_image`` take it as it is, so a second pass on the residual never leaves the device."""
+        if which not in ("subtr", "add"):
+            raise ValueError("which should be 'subtr' or 'add'")
+        if not self._fitted or not self.keep_views:
+            raise AttributeError("no residual: firstfit() has not fitted any seed, or keep_views was False")
+        if self._fitter is None:
+            raise AttributeError("no residual: the fitter was released (release())")
+        self._check_stack()
+        h = C.c_void_p()
+        L.check(L.lib().ia3_fit_view_residual_dev(self._fitter, 0 if which == "subtr" else 1, C.byref(h)))
+        return L.DeviceStack(h, (self.sz, self.sx, self.sy), np.float32)
 
     # -- reference API -----------------------------------------------------------------------
     def firstfit(self):
         """External/Fitting_v4.py:590-639 — Voronoi-restricted first fit of every seed."""
         if len(self.centers) > 0:
             self._ensure()
+            self._drop_views()
             L.check(L.lib().ia3_fit_first(self._fitter))
+            if self.keep_views:
+                L.check(L.lib().ia3_fit_snapshot(self._fitter))   # im_subtr is made from these records later
+            self._fitted = True
             self._pull()
 
     def repeatfit(self):
@@ -466,11 +571,11 @@ class iter_fit_seed_points():
             if self._fitter is None:
                 raise AttributeError("repeatfit() called before firstfit()")
             n_iter = C.c_int(0)
+            self._drop_views()
             L.check(L.lib().ia3_fit_repeat(self._fitter, C.byref(n_iter)))
             self.n_iter = int(n_iter.value)
             self._pull()
             self.converged[:] = True
-            self._release()
 
     def stats(self):
         """(number of LM fits run, total function evaluations) so far — for the flop accounting."""

@@ -38,10 +38,12 @@ def _fit_single_image(_im, _id, _chrom_coords, _seeding_args, _fitting_args, _ch
             tables.append(np.array([]))
             continue
         fitter = Fitting_v3.iter_fit_seed_points(_im, seeds.T, *_fitting_args)
+        fitter.keep_views = False   # only the rows are read here
         fitter.firstfit()
         if _check_fitting:
             fitter.repeatfit()
         rows = np.array(fitter.ps)
+        fitter.release()
         if scale is not None:
             rows[:, 0] /= scale
         tables.append(rows)

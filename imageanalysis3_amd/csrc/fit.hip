@@ -1387,6 +1387,7 @@ struct ia3_fitter {
   std::vector<char> kd_stage;       // source of the asynchronous tree upload
   bool cached;         // host_stage holds [counters | n_iter | ctl | overflow | rows] of the finished fit (run_sweeps)
   std::vector<char> host_stage;  // source of the asynchronous setup upload; lives as long as the fitter
+  void* d_snap = nullptr;        // ia3_fit_snapshot: the SeedState array as the first fit left it (a block of its own), or null
 };
 
 namespace {
@@ -1452,6 +1453,7 @@ void ia3_fit_destroy(ia3_fitter* f) {
   if (!f) return;
   if (f->pool) ws_put(f->pool);   // back to the scratch cache; reuse is stream-ordered
   if (f->kd_block) ws_put(f->kd_block);
+  if (f->d_snap) ws_put(f->d_snap);
   if (f->host_stage.capacity() > t_spare_stage.capacity() && f->host_stage.capacity() <= (64u << 20)) t_spare_stage.swap(f->host_stage);
   delete f;
 }
@@ -2118,6 +2120,296 @@ int ia3_gaussfit_voxels(const double* vals, const int* coords_zxy, const int* of
   if (xs) IA3_HIP(hipMemcpyAsync(xs, dxs.p, (size_t)n_fits * NP * sizeof(double), hipMemcpyDeviceToHost, st));
   if (info) IA3_HIP(hipMemcpyAsync(info, dinfo.p, (size_t)n_fits * 2 * sizeof(int), hipMemcpyDeviceToHost, st));
   IA3_HIP(hipStreamSynchronize(st));
+  return IA3_OK;
+}
+
+}  // extern "C"
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Views of a finished fit: what the reference's class leaves on the object besides the rows (External/Fitting_v4.py:
+// 590-683) — gparms (the Voronoi voxel set of every first fit), ims_rec (every fitted Gaussian over its ball), im_subtr
+// and im_add (the image minus the reconstructions).  The fit itself never materialises any of them (header of this file);
+// these kernels render them on request from what it left behind: the SeedState records (as they are now, or as
+// ia3_fit_snapshot kept them after the first fit), the neighbour lists and the tie masks.  One wavefront per seed; nothing
+// here is launched by ia3_fit_run or the per-FOV path.
+//
+// The residual is DEFINED per voxel as ((im - rec_a) - rec_b) - ... over the seeds a < b < ... that have a reconstruction
+// and whose ball holds the voxel, in float64: what the reference's im_subtr is bit for bit, and its im_add up to the
+// rounding order of its in-place updates.  Every voxel inside some ball has one OWNER, the lowest seed
+// whose ball holds it; the owner's wave forms the whole chain and stores it: one writer per voxel, no atomics, the same
+// bits on every run.
+// Precondition (gather_repeat's as well): two seeds whose balls share a voxel are neighbours, i.e. within 2r of each
+// other.  The balls sit on the truncated seed positions, so this holds for integer seeds — what get_seeds returns — and
+// can fail for fractional ones (truncated centres up to 2r apart, the seeds themselves further): such a voxel would have
+// two owners.
+namespace {
+
+// The geometry of one seed's reconstruction from its record — gather_repeat's set-up for a neighbour — and the model on
+// it.  Not inlined: ims_rec and the residual volumes come from different kernels and must agree bit for bit, so both run
+// the same instructions (inlined copies may contract multiply-adds differently).  The price is that a Geom handed over by
+// pointer lives in private memory; the per-slot arrays of the callers stay in registers (their loops are unrolled).
+__device__ __attribute__((noinline)) void view_geom(const SeedState* sj, const double* seed, double min_ws, double max_ws,
+                                                    double init_w, int variant, Geom* g) {
+  FitCfg cj;
+  cj.min_ws = min_ws; cj.max_ws = max_ws; cj.delta = sj->delta; cj.init_w = init_w;
+  cj.variant = variant;
+  cj.iw[0] = cj.iw[1] = cj.iw[2] = 0.0;   // start widths: not part of the model
+  cj.c0[0] = seed[0]; cj.c0[1] = seed[1]; cj.c0[2] = seed[2];
+  double xj[NP];
+#pragma unroll
+  for (int k = 0; k < NP; ++k) xj[k] = sj->x[k];
+  make_geom(xj, cj, *g);
+}
+__device__ __attribute__((noinline)) double view_f0(const Geom* g, int z, int x, int y) {
+  return model_f0(*g, (double)z, (double)x, (double)y);
+}
+__device__ __forceinline__ void view_geom_of(const FitArgs& fa, int j, Geom* g) {
+  view_geom(&fa.state[j], fa.seeds + 3 * (size_t)j, fa.min_ws, fa.max_ws, fa.init_w, fa.variant, g);
+}
+// the ball test of gather_repeat: offsets in [-r, r) on every axis, inside the sphere
+__device__ __forceinline__ bool view_in_ball(int oz, int ox, int oy, int r) {
+  return oz >= -r && oz < r && ox >= -r && ox < r && oy >= -r && oy < r && oz * oz + ox * ox + oy * oy <= r * r;
+}
+
+// gparms: the voxels of every seed's first fit (gather_first decides, so membership is the fit's own), packed to the
+// front in ball order — the place of ball voxel lane + 64 * slot is its rank among the valid ones (ballot + the count of
+// lower lanes, slot by slot).  zxy: n x nball x 3, val: n x nball (image values, exact in float64), cnt: n.
+__global__ __launch_bounds__(64) void view_voxels_k(FitArgs fa, int* __restrict__ cnt, int* __restrict__ zxy,
+                                                    double* __restrict__ val) {
+  __shared__ BallLds bls;
+  const int i = (int)blockIdx.x, lane = threadIdx.x & 63;
+  unsigned valid = 0;
+  double vals[SLOTS];
+  gather_first(fa, i, (IA3_LDS BallLds*)&bls, valid, vals);
+  const int iz = (int)fa.seeds[3 * i], ix = (int)fa.seeds[3 * i + 1], iy = (int)fa.seeds[3 * i + 2];
+  int base = 0;
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) {
+    const bool ok = (valid >> s) & 1u;
+    const unsigned long long m = __ballot(ok);
+    if (ok) {
+      const BallOff o = ball_off(fa.ball, lane + 64 * s);
+      const size_t q = (size_t)i * fa.nball + (size_t)(base + __popcll(m & ((1ull << lane) - 1ull)));
+      zxy[3 * q] = iz + o.dz; zxy[3 * q + 1] = ix + o.dx; zxy[3 * q + 2] = iy + o.dy;
+      val[q] = vals[s];
+    }
+    base += __popcll(m);
+  }
+  if (lane == 0) cnt[i] = base;
+}
+
+// ims_rec: model_f0 of every seed's record over ball ∩ image (no Voronoi restriction), packed the same way.  has: n
+// flags (0: no reconstruction, the reference's scalar NaN); x11 (optional): n x 11, the record's unconstrained
+// parameters and its delta_center.
+__global__ __launch_bounds__(64) void view_recs_k(FitArgs fa, int* __restrict__ cnt, unsigned char* __restrict__ has,
+                                                  double* __restrict__ rec, double* __restrict__ x11) {
+  const int i = (int)blockIdx.x, lane = threadIdx.x & 63;
+  const SeedState* si = &fa.state[i];
+  const bool hr = si->has_rec != 0;
+  if (x11 && lane < NP + 1) x11[(size_t)i * (NP + 1) + lane] = lane < NP ? si->x[lane] : si->delta;
+  Geom g;
+  if (hr) view_geom_of(fa, i, &g);
+  const int iz = (int)fa.seeds[3 * i], ix = (int)fa.seeds[3 * i + 1], iy = (int)fa.seeds[3 * i + 2];
+  int base = 0;
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) {
+    const int vi = lane + 64 * s;
+    bool ok = false;
+    int z = 0, x = 0, y = 0;
+    if (vi < fa.nball) {
+      const BallOff o = ball_off(fa.ball, vi);
+      z = iz + o.dz; x = ix + o.dx; y = iy + o.dy;
+      ok = z >= 0 && z < fa.Z && x >= 0 && x < fa.X && y >= 0 && y < fa.Y;
+    }
+    const unsigned long long m = __ballot(ok);
+    if (ok && hr) rec[(size_t)i * fa.nball + (size_t)(base + __popcll(m & ((1ull << lane) - 1ull)))] = view_f0(&g, z, x, y);
+    base += __popcll(m);
+  }
+  if (lane == 0) { cnt[i] = base; has[i] = hr ? 1 : 0; }
+}
+
+// residual, pass 1: the image in the output's type
+template <class T>
+__global__ __launch_bounds__(256) void view_cast_k(const void* __restrict__ im, int dtype, size_t n, T* __restrict__ out) {
+  for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < n; k += (size_t)gridDim.x * 256) out[k] = (T)load_voxel(im, dtype, k);
+}
+
+// residual, pass 2: seed i's wave owns the in-image voxels of its ball that no lower seed's ball holds.  Neighbours come
+// in ascending index (list or seed-list scan): the lower ones only take voxels away, then the chain is the seed itself
+// followed by the higher ones that hold the voxel.  T = double (im_subtr / im_add) or float (rounded once at the store).
+template <class T>
+__global__ __launch_bounds__(64) void view_resid_k(FitArgs fa, T* __restrict__ out) {
+  const int i = (int)blockIdx.x, lane = threadIdx.x & 63;
+  const int r = fa.radius;
+  const int iz = (int)fa.seeds[3 * i], ix = (int)fa.seeds[3 * i + 1], iy = (int)fa.seeds[3 * i + 2];
+  unsigned own = 0;
+  int vz[SLOTS], vx[SLOTS], vy[SLOTS];
+  double vals[SLOTS];
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s) {
+    const int vi = lane + 64 * s;
+    vz[s] = 0; vx[s] = 0; vy[s] = 0; vals[s] = 0.0;
+    if (vi < fa.nball) {
+      const BallOff o = ball_off(fa.ball, vi);
+      const int z = iz + o.dz, x = ix + o.dx, y = iy + o.dy;
+      if (z >= 0 && z < fa.Z && x >= 0 && x < fa.X && y >= 0 && y < fa.Y) {
+        own |= 1u << s;
+        vals[s] = load_voxel(fa.ims[0], fa.dtype, ((size_t)z * fa.X + x) * fa.Y + y);
+        vz[s] = z; vx[s] = x; vy[s] = y;
+      }
+    }
+  }
+  bool self_done = false;
+  auto subtract_self = [&]() {
+    self_done = true;
+    if (!fa.state[i].has_rec) return;
+    Geom g;
+    view_geom_of(fa, i, &g);
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s)
+      if (own & (1u << s)) vals[s] -= view_f0(&g, vz[s], vx[s], vy[s]);
+  };
+  each_neighbour(fa, i, [&](int j) {
+    const int jz = (int)fa.seeds[3 * j], jx = (int)fa.seeds[3 * j + 1], jy = (int)fa.seeds[3 * j + 2];
+    if (j < i) {
+#pragma unroll
+      for (int s = 0; s < SLOTS; ++s)
+        if ((own & (1u << s)) && view_in_ball(vz[s] - jz, vx[s] - jx, vy[s] - jy, r)) own &= ~(1u << s);
+      return true;
+    }
+    if (!self_done) subtract_self();
+    if (!fa.state[j].has_rec) return true;
+    Geom gj;
+    view_geom_of(fa, j, &gj);
+#pragma unroll
+    for (int s = 0; s < SLOTS; ++s)
+      if ((own & (1u << s)) && view_in_ball(vz[s] - jz, vx[s] - jx, vy[s] - jy, r)) vals[s] -= view_f0(&gj, vz[s], vx[s], vy[s]);
+    return true;
+  });
+  if (!self_done) subtract_self();
+#pragma unroll
+  for (int s = 0; s < SLOTS; ++s)
+    if (own & (1u << s)) out[((size_t)vz[s] * fa.X + vx[s]) * fa.Y + vy[s]] = (T)vals[s];
+}
+
+// what every view checks first; a: the kernel arguments with the chosen records (which: 0 = first-fit snapshot, 1 = current)
+int view_args(ia3_fitter* f, int which, FitArgs* a) {
+  if (!f) return set_error(IA3_EINVAL, "null fitter");
+  if (f->ims.size() != 1)
+    return set_error(IA3_EUNSUPPORTED, "views of a fit are made for a fitter of one field of view (this one holds %d)", (int)f->ims.size());
+  if (!f->first_done) return set_error(IA3_EINVAL, "view of a fit before firstfit()");
+  if (which != 0 && which != 1) return set_error(IA3_EINVAL, "which: 0 = first-fit records, 1 = current records");
+  if (which == 0 && f->n > 0 && !f->d_snap) return set_error(IA3_EINVAL, "no first-fit records: ia3_fit_snapshot was not called");
+  *a = make_args(f);
+  if (which == 0) a->state = (SeedState*)f->d_snap;
+  return IA3_OK;
+}
+
+template <class T>
+int view_residual(ia3_fitter* f, const FitArgs& a, T* d_out) {
+  hipStream_t st = stream();
+  const size_t nvox = (size_t)a.Z * a.X * a.Y;
+  size_t blocks = (nvox + 255) / 256;
+  const size_t cap = (size_t)num_cus() * 32;
+  if (blocks > cap) blocks = cap;
+  if (blocks < 1) blocks = 1;
+  ProfScope ps("fit_view_residual");
+  hipLaunchKernelGGL(view_cast_k<T>, dim3((unsigned)blocks), dim3(256), 0, st, f->im->d, a.dtype, nvox, d_out);
+  if (f->n > 0) hipLaunchKernelGGL(view_resid_k<T>, dim3((unsigned)f->n), dim3(64), 0, st, a, d_out);
+  IA3_KCHECK();
+  return IA3_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int ia3_fit_create_fovs(const ia3_stack* const* ims, const double* const* centers_zxy, const int* n_seeds, int n_fov,
+                        const ia3_fit_params* p, ia3_fitter** out) {
+  if (!ims || !centers_zxy || !n_seeds || n_fov < 1) return set_error(IA3_EINVAL, "bad argument");
+  std::vector<FovSeeds> v((size_t)n_fov);
+  for (int k = 0; k < n_fov; ++k) v[(size_t)k] = FovSeeds{ims[k], centers_zxy[k], nullptr, n_seeds[k]};
+  return fit_create_impl(v.data(), n_fov, p, out);
+}
+
+int ia3_fit_snapshot(ia3_fitter* f) {
+  FitArgs a;
+  int rc = view_args(f, 1, &a); if (rc) return rc;
+  if (f->n == 0) return IA3_OK;
+  if (!f->d_snap) {
+    f->d_snap = ws_get(sizeof(SeedState) * (size_t)f->n);
+    if (!f->d_snap) return IA3_ENOMEM;
+  }
+  IA3_HIP(hipMemcpyAsync(f->d_snap, f->d_state, sizeof(SeedState) * (size_t)f->n, hipMemcpyDeviceToDevice, stream()));
+  return IA3_OK;
+}
+
+int ia3_fit_view_voxels(ia3_fitter* f, int* counts, int* zxy, double* vals) {
+  FitArgs a;
+  int rc = view_args(f, 1, &a); if (rc) return rc;
+  if (!counts || !zxy || !vals) return set_error(IA3_EINVAL, "null argument");
+  const size_t n = (size_t)f->n, nb = (size_t)f->nball;
+  if (n == 0) return IA3_OK;
+  Scratch dc(n * sizeof(int)), dz(n * nb * 3 * sizeof(int)), dv(n * nb * sizeof(double));
+  if (!dc.p || !dz.p || !dv.p) return IA3_ENOMEM;
+  hipStream_t st = stream();
+  {
+    ProfScope ps("fit_view_voxels");
+    hipLaunchKernelGGL(view_voxels_k, dim3((unsigned)n), dim3(64), 0, st, a, dc.as<int>(), dz.as<int>(), dv.as<double>());
+  }
+  IA3_KCHECK();
+  IA3_HIP(hipMemcpyAsync(counts, dc.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  IA3_HIP(hipMemcpyAsync(zxy, dz.p, n * nb * 3 * sizeof(int), hipMemcpyDeviceToHost, st));
+  IA3_HIP(hipMemcpyAsync(vals, dv.p, n * nb * sizeof(double), hipMemcpyDeviceToHost, st));
+  IA3_HIP(hipStreamSynchronize(st));
+  return IA3_OK;
+}
+
+int ia3_fit_view_recs(ia3_fitter* f, int which, int* counts, uint8_t* has_rec, double* recs, double* x11) {
+  FitArgs a;
+  int rc = view_args(f, which, &a); if (rc) return rc;
+  if (!counts || !has_rec || !recs) return set_error(IA3_EINVAL, "null argument");
+  const size_t n = (size_t)f->n, nb = (size_t)f->nball;
+  if (n == 0) return IA3_OK;
+  Scratch dc(n * sizeof(int)), dh(n), dr(n * nb * sizeof(double)), dx(n * (NP + 1) * sizeof(double));
+  if (!dc.p || !dh.p || !dr.p || !dx.p) return IA3_ENOMEM;
+  hipStream_t st = stream();
+  {
+    ProfScope ps("fit_view_recs");
+    hipLaunchKernelGGL(view_recs_k, dim3((unsigned)n), dim3(64), 0, st, a, dc.as<int>(), dh.as<unsigned char>(), dr.as<double>(),
+                       x11 ? dx.as<double>() : (double*)nullptr);
+  }
+  IA3_KCHECK();
+  IA3_HIP(hipMemcpyAsync(counts, dc.p, n * sizeof(int), hipMemcpyDeviceToHost, st));
+  IA3_HIP(hipMemcpyAsync(has_rec, dh.p, n, hipMemcpyDeviceToHost, st));
+  IA3_HIP(hipMemcpyAsync(recs, dr.p, n * nb * sizeof(double), hipMemcpyDeviceToHost, st));
+  if (x11) IA3_HIP(hipMemcpyAsync(x11, dx.p, n * (NP + 1) * sizeof(double), hipMemcpyDeviceToHost, st));
+  IA3_HIP(hipStreamSynchronize(st));
+  return IA3_OK;
+}
+
+int ia3_fit_view_residual(ia3_fitter* f, int which, double* out) {
+  FitArgs a;
+  int rc = view_args(f, which, &a); if (rc) return rc;
+  const size_t bytes = (size_t)a.Z * a.X * a.Y * sizeof(double);
+  Scratch d(bytes);
+  if (!d.p) return IA3_ENOMEM;
+  rc = view_residual<double>(f, a, d.as<double>()); if (rc) return rc;
+  hipStream_t st = stream();
+  if (out) IA3_HIP(hipMemcpyAsync(out, d.p, bytes, hipMemcpyDeviceToHost, st));
+  IA3_HIP(hipStreamSynchronize(st));
+  return IA3_OK;
+}
+
+int ia3_fit_view_residual_dev(ia3_fitter* f, int which, ia3_stack** out) {
+  FitArgs a;
+  int rc = view_args(f, which, &a); if (rc) return rc;
+  if (!out) return set_error(IA3_EINVAL, "null argument");
+  ia3_stack* s = nullptr;
+  rc = ia3_stack_alloc(IA3_F32, a.Z, a.X, a.Y, &s); if (rc) return rc;
+  rc = view_residual<float>(f, a, (float*)s->d);
+  if (rc) { ia3_stack_free(s); return rc; }
+  *out = s;
   return IA3_OK;
 }
 

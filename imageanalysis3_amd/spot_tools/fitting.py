@@ -23,7 +23,16 @@ def get_seeds(im, max_num_seeds=None, th_seed=150,
     """spot_tools/fitting.py:20-154 — DoG local-maximum seeding.
 
     Returns (N,3) float64 [z,x,y] (or (N,4) with the DoG height), brightest first.
-    Device path: ia3_dog_seed (gauss.hip + seed.hip)."""
+    Device path: ia3_dog_seed (gauss.hip + seed.hip).  A resident ``DeviceStack`` (a corrected image, the residual of
+    a fit) is seeded where it is."""
+    if isinstance(im, L.DeviceStack):
+        return _get_seeds_dev(im, max_num_seeds=max_num_seeds, th_seed=th_seed, th_seed_per=th_seed_per,
+                              use_percentile=use_percentile, sel_center=sel_center, seed_radius=seed_radius,
+                              gfilt_size=gfilt_size, background_gfilt_size=background_gfilt_size, filt_size=filt_size,
+                              min_edge_distance=min_edge_distance, use_dynamic_th=use_dynamic_th,
+                              dynamic_niters=dynamic_niters, min_dynamic_seeds=min_dynamic_seeds,
+                              remove_hot_pixel=remove_hot_pixel, hot_pixel_th=hot_pixel_th, return_h=return_h,
+                              verbose=verbose)
     if not isinstance(im, np.ndarray):
         raise TypeError(f"image given should be a numpy.ndarray, but {type(im)} is given.")
     if th_seed_per >= 100 or th_seed_per <= 50:
@@ -173,9 +182,11 @@ def fit_fov_image(im, channel, seeds=None,
                 print(f"{len(_seeds)} selected by mask, ", end='')
         _fitter = Fitting_v4.iter_fit_seed_points(_stack, np.asarray(_seeds).T, radius_fit=fit_radius,
                                                   **fitting_args)
+        _fitter.keep_views = False   # only the rows are read here
         _fitter.firstfit()
         _fitter.repeatfit()
         _spots = np.array(_fitter.ps)
+        _fitter.release()
         _spots = _spots[np.sum(np.isnan(_spots), axis=1) == 0]               # :232
         if remove_boundary_points:                                           # :234-237
             _kept = (_spots[:, 1:4] > np.zeros(3)).all(1) * (_spots[:, 1:4] < np.array(_shape)).all(1)
@@ -303,9 +314,11 @@ def get_centers(im, seeds=None, th_seed=150,
         seeding.update(seed_kwargs)
         seeds = get_seeds(im, **seeding)
     fitter = Fitting_v4.iter_fit_seed_points(im, seeds.T, radius_fit=fit_radius)
+    fitter.keep_views = False   # only the rows are read here
     fitter.firstfit()
     fitter.repeatfit()
     rows = fitter.ps
+    fitter.release()
     if len(rows) == 0:
         if verbose:
             print("-- no points fitted, return empty array.")

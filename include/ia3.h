@@ -394,6 +394,40 @@ int ia3_fit_stats(ia3_fitter* f, int64_t* total_fits, int64_t* total_nfev);
 int ia3_fit_counters(ia3_fitter* f, uint64_t* out32);
 void ia3_fit_destroy(ia3_fitter* f);
 
+/* ---- views of a finished fit: what the reference's class leaves on the object besides the rows (gparms, ims_rec,
+ * im_subtr, im_add; External/Fitting_v4.py:590-683).  The fit never materialises them; each call below renders one on
+ * request from the fitter's per-seed records, with kernels of its own — ia3_fit_run and the per-FOV entries launch none of
+ * this.  For a fitter of ONE field of view after ia3_fit_first / ia3_fit_run (several fields: IA3_EUNSUPPORTED, before the
+ * first fit: IA3_EINVAL).  `which` selects the records: 0 = as ia3_fit_snapshot kept them (IA3_EINVAL without one), 1 = as
+ * they are now.  nball below = voxels of the integer ball of radius_fit (offsets in [-r, r), 512 for radius 5). */
+/* keeps a copy of the per-seed records as they are now (device to device, a block of its own from the scratch cache,
+ * overwritten by the next call): called right after ia3_fit_first it is what im_subtr is made from later. */
+int ia3_fit_snapshot(ia3_fitter* f);
+/* gparms: per seed the voxels of its first fit — ball, image bounds, Voronoi cell with the fit's own tie decisions — packed
+ * to the front in np.indices order of the ball.  counts: n ints; zxy: n x nball x 3 ints; vals: n x nball doubles (the image
+ * values, exact); rows are filled up to counts[i].  The set depends on the seeds alone, hence no `which`. */
+int ia3_fit_view_voxels(ia3_fitter* f, int* counts, int* zxy, double* vals);
+/* ims_rec: per seed the model without background (GaussianFit.get_im) of its record over ball ∩ image, no Voronoi
+ * restriction, packed the same way.  counts: n ints; has_rec: n bytes, 0 = no fit of this seed has succeeded (the
+ * reference's scalar NaN; its row of recs is not written); recs: n x nball doubles; x11 (may be NULL): n x 11 doubles, the
+ * record itself: the ten unconstrained parameters [bk, h, c0, c1, c2, w0, w1, w2, pp, tp] and the delta_center of that fit. */
+int ia3_fit_view_recs(ia3_fitter* f, int which, int* counts, uint8_t* has_rec, double* recs, double* x11);
+/* im_subtr (which = 0) / im_add (which = 1): Z x X x Y doubles on the host, per voxel ((im - rec_a) - rec_b) - ... over the
+ * seeds a < b < ... with a reconstruction whose ball holds the voxel.  Bit-equal to the reference's im_subtr; its im_add is
+ * updated in place and differs by the rounding order.  out == NULL: rendered on the device, waited for,
+ * not copied (timing).  Same bits on every run.  Precondition: seeds whose balls share a voxel are within 2 radius_fit of
+ * each other, which integer seed positions (ia3_dog_seed's) guarantee; the balls sit on the truncated positions, so
+ * fractional seeds just beyond that distance would give a shared voxel two owners. */
+int ia3_fit_view_residual(ia3_fitter* f, int which, double* out);
+/* the same residual rounded once to float32 into a new resident stack (free it with ia3_stack_free): what a second
+ * seeding pass reads; no float64 volume is made. */
+int ia3_fit_view_residual_dev(ia3_fitter* f, int which, ia3_stack** out);
+/* ia3_fit_create for several fields of view of the same shape and dtype (at most 64) in one fitter, seeds of field k =
+ * n_seeds[k] x 3 doubles at centers_zxy[k]: neighbours and sweeps stay inside a field, the work list runs over all of them
+ * (what ia3_fit_fovs makes per group).  Rows, success and nvox come back field after field. */
+int ia3_fit_create_fovs(const ia3_stack* const* ims, const double* const* centers_zxy, const int* n_seeds, int n_fov,
+                        const ia3_fit_params* p, ia3_fitter** out);
+
 /* External/Fitting_v4.py:165-396 GaussianFit(im, X, center, ...).fit() for a batch of explicit voxel lists
  * (<= 512 voxels each): vals / coords_zxy concatenated, off[n_fits+1]; cfg4 = (delta_center, min_w, max_w,
  * init_w) per fit; kind = dtype class of the caller's values (0 float32, 1 integer, 2 float64), which selects
