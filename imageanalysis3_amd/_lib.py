@@ -42,6 +42,7 @@ EXPORTS = [
     "ia3_gaussian_filter2d_f64_dev", "ia3_gaussian_filter2d_f64", "ia3_illumination_image_profile_dev",
     "ia3_crop_pairs_dev", "ia3_poly_field_dev", "ia3_buffer_alloc", "ia3_buffer_download", "ia3_bleedthrough_profile_dev",
     "ia3_fastfit_normalize_dev", "ia3_fastfit_seeds_dev", "ia3_fastfit_moments_dev", "ia3_fastfit_voxels",
+    "ia3_label_boxes_dev", "ia3_cube_labels_dev", "ia3_cube_max_dev", "ia3_cube_gather_dev",
 ]
 
 
@@ -388,6 +389,60 @@ def crop_pairs(stack_a, centers_a, crop, stack_b=None, centers_b=None, regress=F
                                    ptr(boxes_a), None if boxes_b is None else ptr(boxes_b),
                                    *([dptr(r) for r in reg] if regress else [None, None, None])))
     return boxes_a, boxes_b, reg
+
+
+CUBE_MAX_RADIUS = 10          # largest search radius of the cube lookups (csrc/ia3_labels.h)
+IA3_TUNE_COL_RTC = 17
+
+
+def _centres(centers_zxy):
+    """(n, 3) C-contiguous float64 copy of a table of z, x, y centres."""
+    c = np.ascontiguousarray(centers_zxy, dtype=np.float64)
+    if c.ndim != 2 or c.shape[1] != 3:
+        raise ValueError("centres should be an (n, 3) table of z, x, y, got shape %s" % (c.shape,))
+    return c
+
+
+def label_boxes(labels, max_label=65535):
+    """``ia3_label_boxes_dev``: the (max_label + 1, 7) int32 table [count, z0, z1, x0, x1, y0, y1] of a resident uint16
+    label stack, row l for label l ([start, stop) bounds without a margin; zeros for a label that does not occur)."""
+    out = np.empty((int(max_label) + 1, 7), dtype=np.int32)
+    check(lib().ia3_label_boxes_dev(labels._h, int(max_label), out.ctypes.data_as(C.POINTER(C.c_int))))
+    return out
+
+
+def cube_labels(labels, centers_zxy, radius, target=None):
+    """``ia3_cube_labels_dev``: per centre the most frequent positive label of the clamped cube of ``radius`` around it
+    (-1: none), or, with ``target`` (one label per centre), 1 where the cube holds that label and -1 where not.  int32."""
+    c = _centres(centers_zxy)
+    out = np.empty(len(c), dtype=np.int32)
+    t = None
+    if target is not None:
+        t = np.ascontiguousarray(target, dtype=np.int32).ravel()
+        if len(t) != len(c):
+            raise ValueError("cube_labels: %d centres, %d target labels" % (len(c), len(t)))
+    check(lib().ia3_cube_labels_dev(labels._h, dptr(c), len(c), int(radius),
+                                    None if t is None else t.ctypes.data_as(C.POINTER(C.c_int)),
+                                    out.ctypes.data_as(C.POINTER(C.c_int))))
+    return out
+
+
+def cube_max(stack, centers_zxy, radius):
+    """``ia3_cube_max_dev``: per centre the largest value of the clamped cube of ``radius`` around it, in the stack dtype
+    (NaN where a float32 cube holds one)."""
+    c = _centres(centers_zxy)
+    out = np.empty(len(c), dtype=stack.dtype)
+    check(lib().ia3_cube_max_dev(stack._h, dptr(c), len(c), int(radius), ptr(out)))
+    return out
+
+
+def cube_gather(stack, centers_zxy, radius):
+    """``ia3_cube_gather_dev``: the (n, (2 radius + 1)^3) matrix of the clamped cubes, in the stack dtype; columns in C
+    order of the offsets (dz, dx, dy)."""
+    c = _centres(centers_zxy)
+    out = np.empty((len(c), (2 * int(radius) + 1) ** 3), dtype=stack.dtype)
+    check(lib().ia3_cube_gather_dev(stack._h, dptr(c), len(c), int(radius), ptr(out)))
+    return out
 
 
 def poly_columns(order):

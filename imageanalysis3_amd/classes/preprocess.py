@@ -3,7 +3,8 @@
 The 11-column row naming, ``ImageCrop`` / ``ImageCrop_3d`` ([start, stop) boxes) and the ``Spots3D`` ndarray view
 (own implementations behind the reference's interface).  The reference's ``DaxProcesser`` step class is a CALLER of the
 hot path and stays the reference's own: the copy the end-to-end parity fixtures run through lives with the
-tests (tests/harness/dax_processer.py), not in this package.
+tests (tests/harness/dax_processer.py), not in this package.  Its per-cell spot caller is here as the flat function
+``fit_spots_by_segmentation`` (:1093-1153), because what it does between the fits is device work on the label stack.
 """
 import numpy as np
 from .. import _image_size
@@ -172,3 +173,61 @@ class Spots3D(np.ndarray):
 
     def to_intensities(self):
         return np.array(self[:, getattr(self, 'intensity_index', 0) or 0])
+
+
+def fit_spots_by_segmentation(im, channel, seg_label, drift=None, th_seed=500, num_spots=None,
+                              fitting_kwargs={}, segment_search_radius=3, verbose=False):
+    """classes/preprocess.py:1093-1153 ``DaxProcesser._fit_spots_by_segmentation`` as a flat function: for every label
+    > 0 of ``seg_label`` in ascending order, ``fit_fov_image`` on the label's bounding box (margin one voxel — the
+    reference's call hands its ``3`` to ``cell_id``, not to the margin — moved against ``drift`` by whole voxels and
+    clipped, :95-98), the rows moved back to image coordinates and kept when the cube of ``segment_search_radius`` around
+    them in the unshifted label image holds the label.  Returns ``(spots (M, 11) float32, cell_ids (M,) int32)``, or
+    ``(np.array([]), np.array([]))`` when nothing is kept.
+
+    ``im`` and ``seg_label`` may each be an ndarray or a resident ``DeviceStack`` (labels: uint16).  The boxes of all
+    labels come from one device pass over the label stack, the crops are cut on the device and the keep test of all rows
+    is one launch: the host never walks the label image (an ndarray is converted to uint16 and uploaded, that is all).
+    A crop has whatever depth its cell has: depths without a built-in column kernel take the sliding-window pass here
+    (same bits) instead of starting the run-time compiler once per depth (IA3_TUNE_COL_RTC, this thread, this call)."""
+    from .. import _lib as L
+    from ..spot_tools.fitting import fit_fov_image
+    from ..segmentation_tools.cell import MAX_LABEL, _grow
+    from .partition_spots import _device_form, _Resident
+    if not isinstance(im, (np.ndarray, L.DeviceStack)):
+        raise TypeError(f"image given should be a numpy.ndarray, but {type(im)} is given.")
+    _form, _ = _device_form(seg_label, vote=True)
+    if tuple(_form.shape) != tuple(im.shape):
+        raise IndexError(f"seg_label of shape {tuple(_form.shape)} given for an image of shape {tuple(im.shape)}")
+    _shape = tuple(int(_n) for _n in im.shape)
+    _drift = np.zeros(3) if drift is None else np.asarray(drift, dtype=np.float64)
+    _tables, _owners = [], []
+    with _Resident(_form) as _labels, _Resident(im if isinstance(im, L.DeviceStack) else L.as_stack_array(im)) as _stack:
+        _table = L.label_boxes(_labels, MAX_LABEL)
+        _cell_ids = np.nonzero(_table[:, 0] > 0)[0]
+        _boxes = _grow(_table[_cell_ids, 1:].reshape(-1, 3, 2), 1, _shape)
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_COL_RTC, 0))
+        try:
+            for _cell_id, _box in zip(_cell_ids, _boxes):
+                _drift_crop = ImageCrop_3d(_box, _shape).translate_drift(drift=_drift)
+                if (_drift_crop.array[:, 1] <= _drift_crop.array[:, 0]).any():
+                    continue   # the drift moves this cell's box out of the image
+                with _stack.crop(_drift_crop.array) as _local_im:
+                    _spots = fit_fov_image(_local_im, str(channel), th_seed=th_seed, max_num_seeds=num_spots,
+                                           verbose=verbose, **fitting_kwargs)
+                if len(_spots) > 0:
+                    _spots = np.array(_spots)
+                    _spots[:, _spot_coord_inds] = _spots[:, _spot_coord_inds] + _drift_crop.array[:, 0]
+                    _tables.append(_spots)
+                    _owners.append(np.full(len(_spots), _cell_id, dtype=np.int32))
+        finally:
+            L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_COL_RTC, 1))
+        if _tables:
+            _all_spots, _all_cell_ids = np.concatenate(_tables), np.concatenate(_owners)
+            # keep spots within their cell's mask (:1132-1134): all rows of all cells in one launch
+            _kept = L.cube_labels(_labels, _all_spots[:, _spot_coord_inds], int(segment_search_radius),
+                                  target=_all_cell_ids) > 0
+            _all_spots, _all_cell_ids = _all_spots[_kept], _all_cell_ids[_kept]
+            if len(_all_spots) > 0:
+                return _all_spots, _all_cell_ids
+    print("No spots detected.")
+    return np.array([]), np.array([])

@@ -38,6 +38,7 @@ std::vector<RtcRows> g_rtc_rows;
 pid_t g_rtc_pid = 0;
 int g_rtc_dev = -1;
 constexpr int RTC_R = 30, RTC_RF = 3;   // the radii the translation units are built for (gauss_col.inc)
+thread_local bool t_rtc_on = true;      // IA3_TUNE_COL_RTC: off = this thread uses what is loaded and compiles nothing
 
 // the two kernels of (dtype, depth); nullptr when the run-time path is not available (the caller then reports
 // FOLD_NOT_COVERED and the sliding-window kernels run).  Called with g_rtc_mu held.
@@ -47,6 +48,7 @@ const RtcDepth* rtc_depth_locked(bool f32, int Z) {
   if (g_rtc_pid != getpid() || g_rtc_dev != dev) { g_rtc.clear(); g_rtc_rows.clear(); g_rtc_pid = getpid(); g_rtc_dev = dev; }
   RtcDepth& d = g_rtc[Z * 2 + (f32 ? 1 : 0)];
   if (d.tried) return d.axis0 ? &d : nullptr;
+  if (!t_rtc_on) return nullptr;   // (not marked as tried: a later call with the switch on still gets its kernels)
   d.tried = true;
   if (Z < 16 || Z > 64) return nullptr;
   char pre[512];
@@ -146,6 +148,8 @@ int folded_pair_u16(const uint16_t* src, int Z, size_t plane, const Taps& bt, ui
     default: return rtc_launch(false, Z, src, plane, bt, IA3_MODE_REFLECT, dst, ft, fdst, s, cert, smin, sabs, Y, smx, true);
   }
 }
+
+void set_column_rtc(bool on) { t_rtc_on = on; }
 
 // 0: no column kernel for this depth (the sliding-window kernels run), 1: a translation unit of the library,
 // 2: compiled at run time (now, or taken from the cache)

@@ -27,6 +27,7 @@ inline bool fold_depth(int Z) {
 constexpr int FOLD_NOT_COVERED = 1;   // this depth / these radii have no column kernel: nothing was queued
 constexpr int FOLD_NO_FORK = 2;       // dog_pair_t: no auxiliary stream, everything ran on the main one (nothing to join)
 int column_kernel_source(bool f32, int Z);   // gauss_col_dispatch.hip: 0 none, 1 built in, 2 compiled at run time
+void set_column_rtc(bool on);   // IA3_TUNE_COL_RTC: may this thread's calls compile the kernels of a new depth (default: yes)
 int folded_axis0_f32(const float* src, int Z, size_t plane, const Taps& t, int mode, float* dst, hipStream_t s, int cert);
 int folded_axis0_u16(const uint16_t* src, int Z, size_t plane, const Taps& t, int mode, uint16_t* dst, hipStream_t s, int cert);
 int folded_pair_f32(const float* src, int Z, size_t plane, const Taps& bt, float* dst, const Taps& ft, float* fdst, hipStream_t s, int cert,

@@ -174,7 +174,14 @@ def fit_fov_image(im, channel, seeds=None,
                 print(f"{len(_seeds)} given, ", end='')
         if len(_seeds) == 0:
             return np.array([])
-        if seed_mask is not None:                                            # :210-218
+        if isinstance(seed_mask, L.DeviceStack):                             # :210-218 on a mask that is resident
+            if tuple(seed_mask.shape) != _shape:                             # (e.g. a label stack warped on the device):
+                raise IndexError(f"seed_mask of shape {tuple(seed_mask.shape)} given for an image of shape {_shape}")
+            _sel = L.cube_max(seed_mask, _seeds[:, :len(_shape)], 0) > 0     # the voxel at the rounded seed, radius 0
+            _seeds = _seeds[_sel] if _sel.any() else np.array([])
+            if verbose:
+                print(f"{len(_seeds)} selected by mask, ", end='')
+        elif seed_mask is not None:
             _idx = np.round(_seeds[:, :len(_shape)]).astype(np.int32)
             _sel = seed_mask[tuple(_idx.T)] > 0
             _seeds = _seeds[_sel] if _sel.any() else np.array([])

@@ -140,6 +140,11 @@ int ia3_profile_collect(char* buf, int len); /* "kernel,count,total_ms\n" lines 
  * level 0 yields fewer than min_dynamic_seeds seeds; 0 = every plane of every tile is filtered and tested, list at the
  * lowest level.  Seeds are identical bit for bit. */
 #define IA3_TUNE_SEED_SKIP 16
+/* IA3_TUNE_COL_RTC: per calling thread.  1 (default) = a stack depth without a built-in column kernel has it compiled at
+ * run time the first time it is met (see ia3_prepare_depth); 0 = on this thread such a depth takes the sliding-window
+ * pass unless its kernels are already loaded: no call starts the compiler.  fit_spots_by_segmentation, which filters one
+ * crop per cell, each of a depth of its own, sets it around its loop.  Results are identical bit for bit. */
+#define IA3_TUNE_COL_RTC 17
 /* IA3_DEBUG_FIT_MAXFEV: PROFILING ONLY, changes results: > 0 caps the function evaluations of every fit (MINPACK's maxfev),
  * which splits the fit kernel's time into its fixed and its per-evaluation part; 0 (default) = the reference's limits. */
 #define IA3_DEBUG_FIT_MAXFEV 100
@@ -580,6 +585,29 @@ int ia3_warp3d_dev(const ia3_stack* im, const double* drift, const void* field_d
 
 /* new resident stack = s[z0:z1, x0:x1, y0:y1] (drift crops, correction_tools/alignment.py:617-622) */
 int ia3_stack_crop(const ia3_stack* s, int z0, int z1, int x0, int x1, int y0, int y1, ia3_stack** out);
+
+/* ---- segmentation label images (labels.hip) ------------------------------------------------------
+ * A label (or mask) stack is an ordinary IA3_U16 stack; every result below is integer work, the reference's bit for bit
+ * and the same on every run.
+ * segmentation_tools/cell.py:598-611 segmentation_mask_2_bounding_box for every cell at once, in one pass over the
+ * stack: out7 = (max_label + 1) rows [count, z0, z1, x0, x1, y0, y1] (host), row l the voxel count and the tight
+ * [start, stop) bounds of label l, no margin; all zero for a label that does not occur and for row 0.  Labels above
+ * max_label (1..65535) are passed over.  Stacks of up to 2^31 - 1 voxels (IA3_EUNSUPPORTED above). */
+int ia3_label_boxes_dev(const ia3_stack* labels, int max_label, int* out7);
+/* The cube of classes/partition_spots.py:212-236 find_coordinate_intensities around every row of centers_zxy (n x 3
+ * float64, host): the centre rounded half to even (np.round(...).astype(np.int32)), the (2 radius + 1)^3 offsets in C
+ * order of (dz, dx, dy), every index CLAMPED into the image (a cube that hangs over a face reads the face voxels several
+ * times); radius 0..10.  Centres with NaN are outside the contract.  n = 0 launches nothing.
+ * ia3_cube_labels_dev, target NULL: Spots_Partition.spots_to_labels (:113-140): out[i] = the most frequent label > 0 of
+ * the cube, the smallest of equally frequent ones, -1 when the cube holds none.  target given (n ints): out[i] = 1 when
+ * the cube holds target[i], else -1.
+ * ia3_cube_max_dev: spots_to_DAPI (:143-157): out[i] = the largest value of the cube, in the stack dtype; NaN when a
+ * float32 cube holds one.
+ * ia3_cube_gather_dev: the (n, (2 radius + 1)^3) matrix itself, in the stack dtype. */
+int ia3_cube_labels_dev(const ia3_stack* labels, const double* centers_zxy, int n, int radius, const int* target,
+                        int* out);
+int ia3_cube_max_dev(const ia3_stack* im, const double* centers_zxy, int n, int radius, void* out);
+int ia3_cube_gather_dev(const ia3_stack* im, const double* centers_zxy, int n, int radius, void* out);
 
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
