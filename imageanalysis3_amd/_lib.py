@@ -43,6 +43,8 @@ EXPORTS = [
     "ia3_crop_pairs_dev", "ia3_poly_field_dev", "ia3_buffer_alloc", "ia3_buffer_download", "ia3_bleedthrough_profile_dev",
     "ia3_fastfit_normalize_dev", "ia3_fastfit_seeds_dev", "ia3_fastfit_moments_dev", "ia3_fastfit_voxels",
     "ia3_label_boxes_dev", "ia3_cube_labels_dev", "ia3_cube_max_dev", "ia3_cube_gather_dev",
+    "ia3_plane_medians_dev", "ia3_chrom_seed_mask_dev", "ia3_binary_morph_dev", "ia3_binary_fill_holes_dev", "ia3_label_dev",
+    "ia3_label_centers_dev", "ia3_remove_small_labels_dev", "ia3_find_candidate_chromosomes_dev",
 ]
 
 
@@ -73,6 +75,12 @@ class FovJob(C.Structure):
     _fields_ = [("host", C.c_void_p), ("dev", C.c_void_p), ("rows", C.c_void_p), ("capacity", C.c_int),
                 ("n_rows", C.c_int), ("n_seeds", C.c_int), ("n_iter", C.c_int), ("rc", C.c_int),
                 ("fits", C.c_longlong), ("nfev", C.c_longlong), ("voxel_evals", C.c_longlong)]
+
+
+class ChromParams(C.Structure):
+    """ia3_chrom_params (include/ia3.h)."""
+    _fields_ = [("filt_size", C.c_int), ("morphology_size", C.c_int), ("min_label_size", C.c_int),
+                ("binary_per_th", C.c_double)]
 
 
 MOVIE_MAXCH = 8
@@ -443,6 +451,183 @@ def cube_gather(stack, centers_zxy, radius):
     out = np.empty((len(c), (2 * int(radius) + 1) ** 3), dtype=stack.dtype)
     check(lib().ia3_cube_gather_dev(stack._h, dptr(c), len(c), int(radius), ptr(out)))
     return out
+
+
+MORPH_ERODE, MORPH_DILATE, MORPH_CLOSE = 0, 1, 2   # ia3_binary_morph_dev operations
+MORPH_MAX_RADIUS = 2                               # largest ball of the bit-row operators
+CHROM_FILT_SIZES = (1, 5)                          # _filt_size range of the range filter
+MAX_LABELS16 = 65535
+
+
+def stack_devptr(stack):
+    """Device pointer (``c_void_p``) of the voxels of a resident stack."""
+    d = C.c_void_p()
+    check(lib().ia3_stack_info(stack._h, None, None, None, None, C.byref(d)))
+    return C.c_void_p(d.value)
+
+
+class DeviceLabels(object):
+    """int32 labels of a (Z, X, Y) volume in a device buffer (what ``ia3_label_dev`` writes); ``n`` = number of labels."""
+
+    def __init__(self, shape, n=0):
+        self.shape = tuple(int(v) for v in shape)
+        self.dtype = np.dtype(np.int32)
+        self.n = int(n)
+        p = C.c_void_p()
+        check(lib().ia3_buffer_alloc(C.c_size_t(4 * int(np.prod(self.shape))), C.byref(p)))
+        self.devptr = p
+
+    @classmethod
+    def upload(cls, labels, n=None):
+        a = np.ascontiguousarray(labels, dtype=np.int32)
+        if a.ndim != 3:
+            raise IndexError("a 3-D (z,x,y) label volume is required, got ndim=%d" % a.ndim)
+        out = cls.__new__(cls)
+        out.shape, out.dtype = tuple(a.shape), np.dtype(np.int32)
+        out.n = int(a.max()) if n is None and a.size else int(n or 0)
+        p = C.c_void_p()
+        check(lib().ia3_buffer_upload(ptr(a), C.c_size_t(a.nbytes), C.byref(p)))
+        out.devptr = p
+        return out
+
+    def download(self):
+        out = np.empty(self.shape, dtype=np.int32)
+        check(lib().ia3_buffer_download(self.devptr, C.c_size_t(out.nbytes), ptr(out)))
+        return out
+
+    def free(self):
+        if self.devptr is not None:
+            lib().ia3_buffer_free(self.devptr)
+            self.devptr = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+def plane_medians(stack):
+    """``ia3_plane_medians_dev``: ``[np.median(plane) for plane in stack]`` of a resident stack, widened to float64."""
+    out = np.empty(stack.shape[0], dtype=np.float64)
+    check(lib().ia3_plane_medians_dev(stack._h, dptr(out)))
+    return out
+
+
+def chrom_seed_mask(stack, filt_size, binary_per_th):
+    """``ia3_chrom_seed_mask_dev``: (resident uint16 0 / 1 mask, threshold as ``np.float64``)."""
+    out = DeviceStack.empty(stack.shape, np.uint16)
+    th = C.c_double(0)
+    try:
+        check(lib().ia3_chrom_seed_mask_dev(stack._h, int(filt_size), C.c_double(float(binary_per_th)), out._h, C.byref(th)))
+    except Exception:
+        out.free()
+        raise
+    return out, np.float64(th.value)
+
+
+def binary_morph(mask, op, radius, border=0):
+    """``ia3_binary_morph_dev`` on a resident uint16 mask: a new resident 0 / 1 mask."""
+    out = DeviceStack.empty(mask.shape, np.uint16)
+    try:
+        check(lib().ia3_binary_morph_dev(mask._h, int(op), int(radius), 1 if border else 0, out._h))
+    except Exception:
+        out.free()
+        raise
+    return out
+
+
+def binary_fill_holes(mask):
+    """``ia3_binary_fill_holes_dev`` on a resident uint16 mask: a new resident 0 / 1 mask."""
+    out = DeviceStack.empty(mask.shape, np.uint16)
+    try:
+        check(lib().ia3_binary_fill_holes_dev(mask._h, out._h))
+    except Exception:
+        out.free()
+        raise
+    return out
+
+
+def label(mask, labels16=False):
+    """``ia3_label_dev``: ``DeviceLabels`` (int32, ``.n`` components) of a resident uint16 mask; with ``labels16`` also
+    the uint16 label stack: ``(labels, stack)``.  More than 65535 components do not fit that stack: NotImplementedError."""
+    lab = DeviceLabels(mask.shape)
+    out16 = DeviceStack.empty(mask.shape, np.uint16) if labels16 else None
+    n = C.c_int(0)
+    try:
+        check(lib().ia3_label_dev(mask._h, lab.devptr, C.byref(n), None if out16 is None else out16._h))
+    except Exception:
+        lab.free()
+        if out16 is not None:
+            out16.free()
+        raise
+    lab.n = n.value
+    return (lab, out16) if labels16 else lab
+
+
+def _label_volume(labels):
+    """(device pointer, width in bits, shape) of a ``DeviceLabels`` or a resident uint16 label stack."""
+    if isinstance(labels, DeviceLabels):
+        return labels.devptr, 32, labels.shape
+    if np.dtype(labels.dtype) != np.uint16:
+        raise TypeError("a resident label stack is uint16, got %s" % labels.dtype)
+    return stack_devptr(labels), 16, labels.shape
+
+
+def label_centers(labels, max_label):
+    """``ia3_label_centers_dev``: ((max_label, 3) float64 centres, (max_label,) int64 voxel counts) of labels
+    1..max_label of a ``DeviceLabels`` or a resident uint16 label stack."""
+    p, bits, shape = _label_volume(labels)
+    max_label = int(max_label)
+    cen = np.empty((max_label, 3), dtype=np.float64)
+    cnt = np.empty(max_label, dtype=np.int64)
+    check(lib().ia3_label_centers_dev(p, bits, shape[0], shape[1], shape[2], max_label, dptr(cen),
+                                      cnt.ctypes.data_as(C.POINTER(C.c_longlong))))
+    return cen, cnt
+
+
+def remove_small_labels(labels, max_label, min_size):
+    """``ia3_remove_small_labels_dev``: a new volume of the input's kind in which the labels 1..max_label with fewer than
+    ``min_size`` voxels are 0."""
+    p, bits, shape = _label_volume(labels)
+    out = DeviceLabels(shape, labels.n) if bits == 32 else DeviceStack.empty(shape, np.uint16)
+    try:
+        check(lib().ia3_remove_small_labels_dev(p, bits, shape[0], shape[1], shape[2], int(max_label), C.c_longlong(int(min_size)),
+                                                out.devptr if bits == 32 else stack_devptr(out)))
+    except Exception:
+        out.free()
+        raise
+    return out
+
+
+def find_candidate_chromosomes(stack, filt_size, binary_per_th, morphology_size, min_label_size, return_label=False,
+                               capacity=4096):
+    """``ia3_find_candidate_chromosomes_dev`` on a resident stack: ((n, 3) float64 centres, threshold as ``np.float64``,
+    resident uint16 kept-label stack or None)."""
+    p = ChromParams(int(filt_size), int(morphology_size), int(min_label_size), float(binary_per_th))
+    kept = DeviceStack.empty(stack.shape, np.uint16) if return_label else None
+    n, th = C.c_int(0), C.c_double(0)
+    try:
+        while True:
+            coords = np.empty((capacity, 3), dtype=np.float64)
+            rc = lib().ia3_find_candidate_chromosomes_dev(stack._h, C.byref(p), dptr(coords), int(capacity), C.byref(n),
+                                                          C.byref(th), None if kept is None else kept._h)
+            if rc == IA3_ECAPACITY and n.value > capacity:
+                capacity = n.value
+                continue
+            check(rc)
+            break
+    except Exception:
+        if kept is not None:
+            kept.free()
+        raise
+    return coords[:n.value].copy(), np.float64(th.value), kept
 
 
 def poly_columns(order):

@@ -609,6 +609,62 @@ int ia3_cube_labels_dev(const ia3_stack* labels, const double* centers_zxy, int 
 int ia3_cube_max_dev(const ia3_stack* im, const double* centers_zxy, int n, int radius, void* out);
 int ia3_cube_gather_dev(const ia3_stack* im, const double* centers_zxy, int n, int radius, void* out);
 
+/* ---- candidate chromosomes: 3-D binary morphology and labelling (morph.hip) -----------------------
+ * segmentation_tools/chromosome.py:264-361 find_candidate_chromosomes on a resident stack, and the operators it is made
+ * of.  A mask is an IA3_U16 stack (0 / non-zero in, 0 / 1 out); inside the library it is one bit per voxel.  Order
+ * statistics, comparisons, bit work and integer sums throughout: results equal NumPy / SciPy bit for bit and are the
+ * same on every run.  Stacks of up to 2^31 - 1 voxels (IA3_EUNSUPPORTED above: int32 parents and labels).
+ *
+ * ia3_plane_medians_dev: out[z] = np.median(im[z]) as chromosome.py:296 divides by it, for all planes in one segmented
+ * radix select: float64 (mean of the two middle values for an even count) for a uint16 stack; for a float32 stack the
+ * float32 median (the two middle values added and halved in float32), widened.  NaN for a plane that holds one. */
+int ia3_plane_medians_dev(const ia3_stack* im, double* out);
+/* :293-311: mask_out = seed > scoreatpercentile(seed, binary_per_th) with the first and last ceil(filt_size / 2) planes,
+ * rows and columns cleared, where seed = maximum_filter - minimum_filter (size filt_size = 1..5, window offsets
+ * -(s / 2) .. s - 1 - s / 2, mode 'nearest') of im[z] / median(im[z]) in float64 (uint16 stack) or float32 (float32
+ * stack).  *threshold = the percentile (float64, exact: a selection over the seed's own values); the compare is strict
+ * and in float64.  IA3_EINVAL when a plane's median is 0 or not finite. */
+int ia3_chrom_seed_mask_dev(const ia3_stack* im, int filt_size, double binary_per_th, ia3_stack* mask_out, double* threshold);
+/* scipy.ndimage.binary_erosion / binary_dilation by skimage.morphology.ball(radius), radius 0..2 (ball(1) is the
+ * 6-neighbour cross); border: what the outside of the volume counts as (0 or 1; SciPy's border_value).
+ * IA3_MORPH_CLOSE = skimage.morphology.closing: dilation, then an erosion for which the outside counts as set (border
+ * is not read).  out may be the input. */
+#define IA3_MORPH_ERODE 0
+#define IA3_MORPH_DILATE 1
+#define IA3_MORPH_CLOSE 2
+int ia3_binary_morph_dev(const ia3_stack* mask, int op, int radius, int border, ia3_stack* out);
+/* scipy.ndimage.binary_fill_holes with the 6-neighbour cross (:319 with _morphology_size 1): every 6-connected component
+ * of the background that touches no face of the volume is set.  out may be the input. */
+int ia3_binary_fill_holes_dev(const ia3_stack* mask, ia3_stack* out);
+/* scipy.ndimage.label, default structure (:325): labels_dev = device buffer of Z * X * Y int32 (ia3_buffer_alloc), 0 for
+ * background and 1..n for the 6-connected components in raster order of their first voxel; *n_out = n.  labels16
+ * (optional): the same as a uint16 stack; IA3_EUNSUPPORTED when n > 65535 (labels_dev and *n_out are complete then). */
+int ia3_label_dev(const ia3_stack* mask, int* labels_dev, int* n_out, ia3_stack* labels16);
+/* Labels are read from device memory: label_bits 32 = an int32 buffer as ia3_label_dev writes it, 16 = the voxels of a
+ * uint16 stack (ia3_stack_info gives its pointer).  Labels above max_label count as background.
+ * ia3_label_centers_dev: for l = 1..max_label, counts[l - 1] = the voxels of l and centers_zxy[3 (l - 1) ..] what
+ * _calculate_binary_center (:4-10) gives for label == l: per axis the mean of the index over the voxels whose index on
+ * that axis is > 0 (integer sum over count in float64; NaN when there is none).
+ * ia3_remove_small_labels_dev: skimage.morphology.remove_small_objects on a labelled array (:337): labels with fewer
+ * than min_size voxels become 0, the others keep their numbers; out_dev has the input's width and may be the input. */
+int ia3_label_centers_dev(const void* labels_dev, int label_bits, int Z, int X, int Y, int max_label, double* centers_zxy,
+                          long long* counts);
+int ia3_remove_small_labels_dev(const void* labels_dev, int label_bits, int Z, int X, int Y, int max_label, long long min_size,
+                                void* out_dev);
+/* find_candidate_chromosomes (:264-361) in one call.  _adjust_layers, _random_walk_beta and _num_threads have no effect
+ * there either: random_walker returns its labels when none of them is 0 (:326 leaves none).  morphology_size 1 only
+ * (IA3_EUNSUPPORTED otherwise, and for more than 65535 components, where the reference wraps).  coords_zxy: capacity x 3
+ * float64, the centres of the kept labels in ascending label order; *n_out their number (IA3_ECAPACITY with *n_out set
+ * when capacity is too small; capacity 0 asks for the number).  kept_labels (optional): the uint16 label stack of :337. */
+typedef struct ia3_chrom_params {
+  int filt_size;            /* _filt_size */
+  int morphology_size;      /* _morphology_size */
+  int min_label_size;       /* _min_label_size */
+  double binary_per_th;     /* _binary_per_th */
+} ia3_chrom_params;
+int ia3_find_candidate_chromosomes_dev(const ia3_stack* im, const ia3_chrom_params* p, double* coords_zxy, int capacity,
+                                       int* n_out, double* threshold, ia3_stack* kept_labels);
+
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
  * Per movie: raw (frames, X, Y) uint16 movie from host memory or a .dax file -> split_im_by_channels
