@@ -19,6 +19,7 @@
 //     row-coalesced.  Long filters (VALU-bound, R >= 16): the axis-1 pass stores each plane transposed and the
 //     axis-2 pass is the strided kernel over that transposed plane, storing transposed again.
 #include "ia3_gauss.h"
+#include "ia3_col_weights.h"
 #include <unistd.h>
 #include <cstring>
 #include <mutex>
@@ -616,13 +617,15 @@ int dog_pair_t(const T* src, int Z, int X, int Y, const Taps& ft, const Taps& bt
   const size_t plane = (size_t)X * Y;
   bool nonneg = true;
   for (int j = 0; j <= RB; ++j) nonneg &= bt.w[j] >= 0.0;
-  const int cert = !nonneg ? -1 : (g_cert == -2 ? 3 * RB + Z + 16 : g_cert);
+  const int cert = !nonneg ? -1 : (g_cert == -2 ? col_guard(Z, RB, IA3_MODE_REFLECT) : g_cert);
   int rc;
   {
     ia3rt::ProfScope ps("gauss_axis0_pair");
     static_assert(RF == 3 && RB == 30, "the radii gauss_col.inc instantiates");
-    if constexpr (std::is_same_v<T, float>) rc = folded_pair_f32(src, Z, plane, bt, dst_zp, ft, tmp, s, cert, smin, sabs, Y, smx);
-    else rc = folded_pair_u16(src, Z, plane, bt, dst_zp, ft, tmp, s, cert, smin, sabs, Y, smx);
+    Taps fh = ft;   // the column kernel runs the short pass on the doubled column: its taps halved (exact)
+    for (int j = 0; j <= RF; ++j) fh.w[j] *= 0.5;
+    if constexpr (std::is_same_v<T, float>) rc = folded_pair_f32(src, Z, plane, bt, dst_zp, fh, tmp, s, cert, smin, sabs, Y, smx);
+    else rc = folded_pair_u16(src, Z, plane, bt, dst_zp, fh, tmp, s, cert, smin, sabs, Y, smx);
   }
   if (rc) return rc;   // FOLD_NOT_COVERED, or an error (negative)
   if (!dst_front) return FOLD_NO_FORK;   // the caller runs axes 1 and 2 of the short filter on tmp itself (seed_front_k)
@@ -710,8 +713,8 @@ int run_fixed(const T* src, int Z, int X, int Y, const Taps& t, int mode, T* dst
     ia3rt::ProfScope ps(nz.c_str());
     bool done = false;
     if constexpr (R >= 16) {
-      if (g_fold_on && cert >= 0 && (size_t)Z * plane * sizeof(T) < 0x7fffffffULL) {   // short stacks: the column-in-registers form (guard: 3R + Z + 3 ulps, see the kernel; 32-bit buffer offsets)
-        const int fc = g_cert == -2 ? 3 * R + Z + 16 : cert;
+      if (g_fold_on && cert >= 0 && (size_t)Z * plane * sizeof(T) < 0x7fffffffULL) {   // short stacks: the column-in-registers form (guard: col_guard, derived at the kernel; 32-bit buffer offsets)
+        const int fc = g_cert == -2 ? col_guard(Z, R, mode) : cert;
         int rc = FOLD_NOT_COVERED;
         if constexpr (R == 30) {   // the depths instantiated (IA3_FOLD_DEPTHS, radius 30); other stacks take the sliding window
           if constexpr (std::is_same_v<T, float>) rc = folded_axis0_f32(src, Z, plane, t, mode, dst, s, fc);
@@ -897,6 +900,13 @@ int ia3_prepare_depth(int dtype, int Z) {
   int rc = ensure_init(); if (rc) return rc;
   if (dtype != IA3_F32 && dtype != IA3_U16) return set_error(IA3_EINVAL, "dtype");
   return ia3g::column_kernel_source(dtype == IA3_F32, Z);
+}
+int ia3_col_guard(int Z, int R, int mode) { return ia3g::col_guard(Z, R, mode); }
+int ia3_col_weights(int Z, int R, int mode, const double* taps, double* out, int cap) {
+  if (Z < 2 || R < 0 || R > 63 || !taps) return set_error(IA3_EINVAL, "ia3_col_weights: depth, radius or taps");
+  const std::vector<double> rows = ia3g::col_evenodd_rows(Z, R, mode, taps);
+  for (size_t i = 0; i < rows.size() && (int)i < cap; ++i) out[i] = rows[i];
+  return (int)rows.size();
 }
 int ia3_set_tuning(int key, int value) {
   if (key == IA3_TUNE_GAUSS_CERT) {

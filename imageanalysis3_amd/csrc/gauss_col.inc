@@ -2,6 +2,7 @@
 // with -DIA3_COL_F32=0/1 -DIA3_COL_Z=<depth>, Makefile: FOLD_DEPTHS): the kernels are long straight-line code, ~7 s each,
 // and the translation units build in parallel.
 #include "ia3_gauss.h"
+#include "ia3_col_weights.h"
 #include <unistd.h>
 #include <cstring>
 #include <mutex>
@@ -14,7 +15,7 @@ using namespace ia3colk;
 
 namespace {
 
-// folded weight rows of gauss_axis0_folded, cached on the device per (Z, R, mode, taps)
+// weight stream of gauss_axis0_folded (ia3_col_weights.h), cached on the device per (Z, R, mode, taps)
 struct FoldKey { int Z, R, mode; std::vector<double> w; };
 struct FoldEntry { FoldKey k; double* d = nullptr; };
 std::mutex g_fold_mu;
@@ -32,17 +33,7 @@ const double* folded_rows(const Taps& t, int mode, hipStream_t s) {
   }
   for (auto& e : g_fold)
     if (e.k.Z == Z && e.k.R == R && e.k.mode == mode && std::memcmp(e.k.w.data(), t.w, (R + 1) * sizeof(double)) == 0) return e.d;
-  std::vector<double> rows;
-  for (int z = 0; z < (Z + 1) / 2; ++z) {
-    const int lo = fold_lo<Z, R>(z), hi = fold_hi<Z, R>(z);
-    for (int p = lo; p <= hi; ++p) {
-      double acc = 0.0;
-      for (int j = -R; j <= R; ++j)
-        if (border_idx(z + j, Z, mode) == p) acc += t.w[j < 0 ? -j : j];
-      rows.push_back(acc);
-    }
-  }
-  rows.resize((rows.size() + 15) / 16 * 16, 0.0);
+  const std::vector<double> rows = col_evenodd_rows(Z, R, mode, t.w);
   FoldEntry e;
   e.k = FoldKey{Z, R, mode, std::vector<double>(t.w, t.w + R + 1)};
   if (hipMalloc((void**)&e.d, rows.size() * sizeof(double)) != hipSuccess) return nullptr;

@@ -6,6 +6,7 @@
 // and only when that is not possible (IA3_RTC=0, no hiprtc, sources not beside the library) the sliding-window kernels
 // (same results, +0.65 ms per 2048 x 2048 x 50 stack).
 #include "ia3_gauss.h"
+#include "ia3_col_weights.h"
 #include <unistd.h>
 #include <cstring>
 #include <cstdio>
@@ -66,22 +67,12 @@ const RtcDepth* rtc_depth_locked(bool f32, int Z) {
   return &d;
 }
 
-// the folded weight rows of a depth (gauss_col.inc: folded_rows<Z, R>, the same sums in the same order), on the device
+// the weight stream of a depth (ia3_col_weights.h, as gauss_col.inc: folded_rows<Z, R>), on the device
 const double* rtc_rows_locked(int Z, const Taps& t, int mode) {
   constexpr int R = RTC_R;
   for (auto& e : g_rtc_rows)
     if (e.Z == Z && e.mode == mode && std::memcmp(e.w.data(), t.w, (R + 1) * sizeof(double)) == 0) return e.d;
-  std::vector<double> rows;
-  for (int z = 0; z < (Z + 1) / 2; ++z) {
-    const int lo = z - R > 0 ? z - R : 0, hi = z + R < Z - 1 ? z + R : Z - 1;
-    for (int p = lo; p <= hi; ++p) {
-      double acc = 0.0;
-      for (int j = -R; j <= R; ++j)
-        if (ia3g::border_idx(z + j, Z, mode) == p) acc += t.w[j < 0 ? -j : j];
-      rows.push_back(acc);
-    }
-  }
-  rows.resize((rows.size() + 15) / 16 * 16, 0.0);
+  const std::vector<double> rows = ia3g::col_evenodd_rows(Z, R, mode, t.w);
   double* d = nullptr;
   if (hipMalloc((void**)&d, rows.size() * sizeof(double)) != hipSuccess) return nullptr;
   if (hipMemcpy(d, rows.data(), rows.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) { (void)hipFree(d); return nullptr; }

@@ -7,39 +7,48 @@ using namespace ia3g;
 // ---- axis 0 of a long filter on a short stack: the whole column in registers, border folded into the weights ----
 // With Z <= 64 planes and R = 30 most taps of an output land on the reflected (or clamped) border, i.e. on a plane
 // the sum already holds: out[z] = sum_p W[z][p] * in[p] with W[z][p] = the taps that map to plane p added up
-// (host, f64), p in [max(0, z-R), min(Z-1, z+R)].  That is 31..Z fused multiply-adds per output instead of R pair
-// additions + R+1 multiply-adds (Z = 50: 42 on average against 66 with the 6-wide chunks), every input is read
-// once, and the rows of z and Z-1-z share their weights (W[Z-1-z][Z-1-p] = W[z][p]).  The order of operations is
-// not NI_Correlate1D's, so this is a certified path like the fused one above: for non-negative data and taps both
-// sums are within (3R+1) resp. (Z+2) * 2^-53 * S of the exact sum S, so the float32 / uint16 value can only differ
-// when the folded sum lies within 3R+Z+3 f64 ulps of a quantisation boundary.  Those outputs, and every output of
-// a thread that saw a sign bit, are recomputed with the reference sequence from global memory.  wf = the folded
-// rows 0 .. (Z-1)/2 packed one after the other (uniform, compile-time offsets -> scalar loads).
-template <int Z, int R> constexpr int fold_lo(int z) { return z - R > 0 ? z - R : 0; }
-template <int Z, int R> constexpr int fold_hi(int z) { return z + R < Z - 1 ? z + R : Z - 1; }
-template <int Z, int R> constexpr int fold_off(int z) {
-  int o = 0;
-  for (int i = 0; i < z; ++i) o += fold_hi<Z, R>(i) - fold_lo<Z, R>(i) + 1;
-  return o;
-}
-// flat position i of the packed weight stream -> its row, and the row offsets, as tables built once per (Z, R) (the
-// kernel asks for them at every one of its ~Z^2 / 2 compile-time positions)
-template <int Z, int R> struct FoldTab {
-  static constexpr int H = (Z + 1) / 2, N = fold_off<Z, R>((Z + 1) / 2);
-  int off[H + 1];
-  int row[N];
-  constexpr FoldTab() : off(), row() {
-    int o = 0;
-    for (int z = 0; z < H; ++z) {
-      off[z] = o;
-      const int n = fold_hi<Z, R>(z) - fold_lo<Z, R>(z) + 1;
-      for (int k = 0; k < n; ++k) row[o + k] = z;
-      o += n;
-    }
-    off[H] = o;
-  }
-};
-template <int Z, int R> inline constexpr FoldTab<Z, R> fold_tab{};
+// (host, f64).  Both border modes give W[Z-1-z][Z-1-p] = W[z][p], so the mirror outputs z and zz = Z-1-z are
+//   a = sum_p W[z][p] v[p],  b = sum_p W[z][p] v[Z-1-p]:
+// the same weights on the same PAIRS of inputs.  With H = Z / 2, E[q] = v[q] + v[Z-1-q], O[q] = v[q] - v[Z-1-q] (formed
+// once per column, as the planes arrive in mirror pairs) and Wp, Wm = (W[z][q] +- W[z][Z-1-q]) / 2 (host, f64):
+//   P = sum_q Wp[z][q] E[q],  M = sum_q Wm[z][q] O[q],  a = P + M,  b = P - M
+// — Z fused multiply-adds and two additions per pair of outputs, where the sums above take 2 * (31 .. Z) (84 on average
+// at Z = 50) and NI_Correlate1D's sequence 2 * (3R + 1).  An odd depth keeps its centre plane: it enters P with its own
+// weight, and the centre row has M = 0 and one output.  wf = the stream of ia3_col_weights.h (uniform, compile-time
+// offsets -> scalar loads).
+//
+// The order of operations is not NI_Correlate1D's, so this is a certified path like the fused one (ia3_gauss_dev.h).
+// u = 2^-53; data and taps non-negative; n = (Z+1)/2 terms in the P chain (H in the M chain); tw = roundings in one
+// W[z][p] (host sums of up to tw + 1 non-negative taps: relative error <= tw u).  First order in u throughout, one
+// unit added at the end for the second-order terms (all factors below are < 2^10).
+//   E^ = (v + v')(1 + e1), O^ = (v - v')(1 + e2), |e| <= u, and |O^| <= E^ (rounding is monotone).
+//   Wp^ = Wp (1 + t), |t| <= (tw + 1) u;  |Wm^ - Wm| <= (tw + 1) u Wp;  |Wm^| <= Wp^.
+//   A chain of n terms (one product, n - 1 FMAs) returns sum_q w_q x_q (1 + g_q), |g_q| <= n u.  All terms of P are
+//   non-negative: |P^ - P| <= (n + tw + 2) u P.  The terms of M are bounded one by one by those of P:
+//   |M^ - M| <= n u P + (tw + 2) u P.
+//   a^ = fl(P^ + M^):  |a^ - a| <= (2n + 2 tw + 4) u P + u a <= (2n + 2 tw + 5) u P, since a <= 2 P; the same for b.
+//   With the second-order unit:  |a^ - a|, |b^ - b| <= C u P,  C = 2n + 2 tw + 6,  P = (a + b) / 2.
+// THE BOUND IS RELATIVE TO P, NOT TO a: a column that is zero in one half and 6e4 in the other has a << b, and its a^
+// is thousands of ulps of a away from a.  Hence
+//   (i)  a pair with |M^| > (1 - 1/K) P^, K = 4 (i.e. min(a^, b^) < P^ / K) takes the reference sequence for both outputs;
+//   (ii) elsewhere P <= K a^ (1 + (n + tw + 7) u), so |a^ - a| <= K C ulp(a^) + 1 (ulp(x) >= u x), and NI_Correlate1D's own
+//        sum r (3R + 1 roundings on non-negative terms) has |r - a| <= (3R + 1) u a <= (3R + 2) ulp(a^): the float32 /
+//        uint16 value of a^ can differ from that of r only when a^ lies within K C + 3R + 3 f64 ulps of a float32 rounding
+//        midpoint / an integer.  The default guard is K C + 3R + 4 (ia3_col_weights.h: col_guard; 326 for Z = 50, R = 30,
+//        'reflect'), and `uncertain` measures in units of at least one ulp.
+// Those outputs (about 1.2e-6 of them at the default guard), and every output of a thread that saw a sign bit, are
+// recomputed with the reference sequence from global memory.
+//
+// RF > 0 (the short pass, below) needs the raw column back, exactly.  It gets the DOUBLED column, 2 v[q] = E + O and
+// 2 v[Z-1-q] = E - O, in place and without a multiplication, and the short filter's taps HALVED (ftaps, host): a factor
+// of two passes through every rounding of NI_Correlate1D's sequence, so the bits are those of the plain sequence.  The
+// two values are exact iff E and O were formed without rounding.  uint16: always.  float32: the sum and the difference
+// of two non-negative values whose exponent fields are at most 28 apart (or one of which is zero) fit in 53 bits.  A sticky
+// test on the raw bits decides per thread: unsigned maximum of the bits, unsigned minimum of bits - 1 (zeros wrap to
+// the top and drop out), exponent fields of the two at most 28 apart and no inf / nan.  A thread that fails it is treated
+// like one that saw a sign bit: reference sequence for the whole column, and its wave takes the short pass from memory.
+constexpr int COL_K = 4;   // rule (i) of the header (ia3_col_weights.h: COL_LOPSIDED_K)
+template <int Z> constexpr int eo_len() { return (Z / 2) * Z + ((Z & 1) ? (Z + 1) / 2 : 0); }
 
 // order-preserving integer key of a stored value and back (strip maxima of the short pass, below)
 template <class T> __device__ __forceinline__ int mx_key(T q);
@@ -49,9 +58,27 @@ template <class T> __device__ __forceinline__ float mx_val(int k);
 template <> __device__ __forceinline__ float mx_val<float>(int k) { return __uint_as_float((unsigned)(k ^ ((k >> 31) & 0x7fffffff))); }
 template <> __device__ __forceinline__ float mx_val<uint16_t>(int k) { return (float)k; }
 
+// one plane of the strip maxima of the short pass (see the kernel; planes come in z order)
+template <class T, int Z>
+__device__ __forceinline__ void strip_max(int z, T qf, int& keep, unsigned lane15, bool mx_row, float* __restrict__ smx, unsigned mx_base) {
+#define IA3_DPP(v, c) __builtin_amdgcn_update_dpp(0, (v), (c), 0xf, 0xf, true)
+  int k = mx_key<T>(qf), t;
+  t = IA3_DPP(k, 0x128); k = k > t ? k : t;   // row_ror:8
+  t = IA3_DPP(k, 0x124); k = k > t ? k : t;
+  t = IA3_DPP(k, 0x122); k = k > t ? k : t;
+  t = IA3_DPP(k, 0x121); k = k > t ? k : t;
+  t = IA3_DPP(k, 0x142); k = k > t ? k : t;   // row_bcast15 (the lower row reads 0: its lanes are not used)
+#undef IA3_DPP
+  keep = lane15 == (unsigned)(z & 15) ? k : keep;
+  if ((z & 15) == 15 || z == Z - 1) {
+    if (mx_row) smx[mx_base + (unsigned)(z & ~15)] = mx_val<T>(keep);
+  }
+}
+
 // RF > 0: the same launch also runs the axis-0 pass of a SHORT filter (radius RF, 'reflect' border) over the column
 // it holds and writes it to fout — the DoG seed detector filters one stack with a short and a long kernel, and the
 // two first passes share every load (NI_Correlate1D's sequence, unfused: the short pass is not a certified path).
+// ftaps = the short filter's taps times 0.5 (see the header).
 template <class T, int Z, int R, int RF>
 __global__ __launch_bounds__(256) void gauss_axis0_folded(const T* __restrict__ in, T* __restrict__ out, size_t plane,
                                                           const double* __restrict__ wf, Taps taps, int mode, int cert,
@@ -80,22 +107,44 @@ __global__ __launch_bounds__(256) void gauss_axis0_folded(const T* __restrict__ 
     gmin[g] = fminf(gmin[g], f);
     if constexpr (sizeof(T) == 4) gabs[g] = fmaxf(gabs[g], fabsf(f));
   };
-  double v[Z];
-  unsigned sbits = 0;
+  // the column as mirror pairs: e[q] = v[q] + v[Z-1-q], o[q] = v[q] - v[Z-1-q]; an odd depth's centre plane is e[H], raw
+  constexpr int H = Z / 2, NP = (Z + 1) / 2;
+  double e[NP], o[H];
+  unsigned bmax = 0u, bmin = ~0u;   // float32: unsigned max of the raw bits (sign bit seen <=> top bit set), min of bits - 1
+  auto track = [&](T t) {
+    if constexpr (sizeof(T) == 4) {
+      const unsigned u = sign_of<T>(t);
+      bmax = bmax > u ? bmax : u;
+      if constexpr (RF > 0) { const unsigned m = u - 1u; bmin = bmin < m ? bmin : m; }
+    }
+  };
 #pragma unroll
-  for (int z = 0; z < Z; ++z) {
-    const T t = buf_ld<T>(rin, voff, (unsigned)z * pbytes);
-    sbits |= sign_of<T>(t);
-    v[z] = (double)t;
+  for (int q = 0; q < H; ++q) {
+    const T t0 = buf_ld<T>(rin, voff, (unsigned)q * pbytes), t1 = buf_ld<T>(rin, voff, (unsigned)(Z - 1 - q) * pbytes);
+    track(t0); track(t1);
+    const double d0 = (double)t0, d1 = (double)t1;
+    e[q] = d0 + d1;
+    o[q] = d0 - d1;
   }
-  unsigned long long redo = 0;   // outputs that need NI_Correlate1D's own sequence (about one thread in 3e4 has one)
-  const bool all = cert < 0 || (int)sbits < 0;
+  if constexpr (Z & 1) {
+    const T t = buf_ld<T>(rin, voff, (unsigned)H * pbytes);
+    track(t);
+    e[H] = (double)t;
+  }
+  bool bad = (int)bmax < 0;   // a sign bit, or (RF > 0) a pair that did not add up exactly: see the header
+  if constexpr (RF > 0 && sizeof(T) == 4) {
+    const unsigned emax = bmax >> 23, emin = (bmin + 1u) >> 23;   // bmin + 1: the smallest non-zero bits, 0 for a column of zeros
+    bad = bad || emax - emin > 28u || emax == 255u;
+  }
+  const bool wave_bad = RF > 0 && __builtin_amdgcn_ballot_w64(bad) != 0ull;   // (uniform)
+  unsigned long long redo = 0;   // outputs that need NI_Correlate1D's own sequence (about one thread in 1.6e4 has one)
+  const bool all = cert < 0 || bad;
   if (all) redo = Z == 64 ? ~0ull : (1ull << Z) - 1;
   if (!all) {
     // the weight stream is read in pieces of CH doubles (scalar loads), the next piece in flight while this one is
     // used; the scheduling barrier keeps the compiler from hoisting every load to the top (and spilling SGPRs)
-    constexpr int N = FoldTab<Z, R>::N, CH = 8, NC = (N + CH - 1) / CH;
-    double a = 0.0, b = 0.0;
+    constexpr int N = eo_len<Z>(), CH = 8, NC = (N + CH - 1) / CH;
+    double P = 0.0, M = 0.0;
     double cur[CH], nxt[CH];
 #pragma unroll
     for (int i = 0; i < CH; ++i) nxt[i] = wf[i];   // the table is padded to a multiple of CH
@@ -110,27 +159,33 @@ __global__ __launch_bounds__(256) void gauss_axis0_folded(const T* __restrict__ 
       auto tap = [&](auto ic) -> bool {
         constexpr int i = c * CH + decltype(ic)::value;
         if constexpr (i < N) {
-          constexpr int z = fold_tab<Z, R>.row[i], zz = Z - 1 - z, lo = fold_lo<Z, R>(z), k = i - fold_tab<Z, R>.off[z];
-          constexpr bool last = i + 1 == fold_tab<Z, R>.off[z + 1];
+          constexpr int z = i / Z < H ? i / Z : H, zz = Z - 1 - z, k = i - z * Z;   // row (z == H: the centre row of an odd depth)
+          constexpr bool centre_row = z == H;
+          constexpr int q = centre_row ? k : k >> 1;
+          constexpr bool minus = !centre_row && (k & 1) != 0 && q < H;
+          constexpr bool last = centre_row ? k == NP - 1 : k == Z - 1;
           const double w = cur[i - c * CH];
-          if constexpr (k == 0) {
-            a = v[lo] * w;
-            if constexpr (zz != z) b = v[Z - 1 - lo] * w;
+          if constexpr (minus) {
+            if constexpr (q == 0) M = o[0] * w; else M = __builtin_fma(o[q], w, M);
           } else {
-            a = __builtin_fma(v[lo + k], w, a);
-            if constexpr (zz != z) b = __builtin_fma(v[Z - 1 - lo - k], w, b);
+            if constexpr (q == 0) P = e[0] * w; else P = __builtin_fma(e[q], w, P);
           }
-          if constexpr (last) {
-            if (uncertain<T>(a, cert)) redo |= 1ull << z;
+          if constexpr (last && centre_row) {
+            if (uncertain<T>(P, cert)) redo |= 1ull << z;
+            const T qa = cvt<T>(P);
+            buf_st<T>(qa, rout, voff, (unsigned)z * pbytes);
+            if constexpr (RF > 0) note(z * NGZ / Z, qa);
+          } else if constexpr (last) {
+            const double a = P + M, b = P - M;
+            const bool lopsided = __builtin_fabs(M) > P * (1.0 - 1.0 / COL_K);   // rule (i); false for P = M = 0, nan is caught by `uncertain`
+            if (uncertain<T>(a, cert) || lopsided) redo |= 1ull << z;
             const T qa = cvt<T>(a);
             buf_st<T>(qa, rout, voff, (unsigned)z * pbytes);
             if constexpr (RF > 0) note(z * NGZ / Z, qa);
-            if constexpr (zz != z) {
-              if (uncertain<T>(b, cert)) redo |= 1ull << zz;
-              const T qb = cvt<T>(b);
-              buf_st<T>(qb, rout, voff, (unsigned)zz * pbytes);
-              if constexpr (RF > 0) note(zz * NGZ / Z, qb);
-            }
+            if (uncertain<T>(b, cert) || lopsided) redo |= 1ull << zz;
+            const T qb = cvt<T>(b);
+            buf_st<T>(qb, rout, voff, (unsigned)zz * pbytes);
+            if constexpr (RF > 0) note(zz * NGZ / Z, qb);
           }
         }
         return true;
@@ -143,7 +198,8 @@ __global__ __launch_bounds__(256) void gauss_axis0_folded(const T* __restrict__ 
   }
   // The short pass runs BEHIND the long one: here no load is in flight, so the raw values no longer sit beside the column
   // of doubles (in front of the long pass the strip maxima below took the kernel from 123 to 164 registers, three waves
-  // per SIMD instead of four, +0.1 ms; here it needs 124).
+  // per SIMD instead of four, +0.1 ms).  It works on the doubled column, made in place from the pairs (header; multiplying
+  // the sums by 0.5 instead made the compiler keep a second, sliding copy of the column: 139 registers, three waves).
   if constexpr (RF > 0) {
     static_assert(Z > RF, "single reflection");
     const __amdgpu_buffer_rsrc_t rf = __builtin_amdgcn_make_buffer_rsrc((void*)fout, (short)0, nbytes, 0x00020000);
@@ -162,35 +218,33 @@ __global__ __launch_bounds__(256) void gauss_axis0_folded(const T* __restrict__ 
     const unsigned mx_base = (p >> 5) * ZP + lane15;   // Y % 32 == 0: strip (row, column / 32) is p / 32; ZP * plane / 32 < 2^31
     int keep = 0;
     const bool want_mx = smx != nullptr;   // (uniform)
-    auto frow = [&](auto zc) -> bool {
-      constexpr int z = decltype(zc)::value;
-      double acc = v[z] * ftaps.w[0];
+    // (a wave with a thread whose pairs are not exact takes the whole short pass from memory, at the end of the kernel)
+    if (!wave_bad) {
 #pragma unroll
-      for (int j = RF; j >= 1; --j) {
-        const int lo = z - j < 0 ? -(z - j) - 1 : z - j, hi = z + j >= Z ? 2 * Z - 1 - (z + j) : z + j;   // compile-time
-        acc = acc + (v[lo] + v[hi]) * ftaps.w[j];
+      for (int q = 0; q < H; ++q) {
+        e[q] = e[q] + o[q];                      // 2 v[q]
+        o[q] = __builtin_fma(o[q], -2.0, e[q]);  // 2 v[q] - 2 O = 2 v[Z-1-q]: representable, so the fused result is exact
+        if ((q & 3) == 3) __builtin_amdgcn_sched_barrier(0);
       }
-      const T qf = cvt<T>(acc);
-      buf_st<T>(qf, rf, voff, (unsigned)z * pbytes);
-      if (want_mx) {
-#define IA3_DPP(v, c) __builtin_amdgcn_update_dpp(0, (v), (c), 0xf, 0xf, true)
-        int k = mx_key<T>(qf), o;
-        o = IA3_DPP(k, 0x128); k = k > o ? k : o;   // row_ror:8
-        o = IA3_DPP(k, 0x124); k = k > o ? k : o;
-        o = IA3_DPP(k, 0x122); k = k > o ? k : o;
-        o = IA3_DPP(k, 0x121); k = k > o ? k : o;
-        o = IA3_DPP(k, 0x142); k = k > o ? k : o;   // row_bcast15 (the lower row reads 0: its lanes are not used)
-#undef IA3_DPP
-        keep = lane15 == (unsigned)(z & 15) ? k : keep;
-        if constexpr ((z & 15) == 15 || z == Z - 1) {
-          if (mx_row) smx[mx_base + (z & ~15)] = mx_val<T>(keep);
+      if constexpr (Z & 1) e[H] = e[H] + e[H];   // the centre plane of an odd depth
+      __builtin_amdgcn_sched_barrier(0);
+      auto frow =[&](auto zc) -> bool {
+        constexpr int z = decltype(zc)::value;
+        auto val = [&](int i) -> double { return i < NP ? e[i] : o[Z - 1 - i]; };   // (compile-time index)
+        double acc = val(z) * ftaps.w[0];
+#pragma unroll
+        for (int j = RF; j >= 1; --j) {
+          const int lo = z - j < 0 ? -(z - j) - 1 : z - j, hi = z + j >= Z ? 2 * Z - 1 - (z + j) : z + j;   // compile-time
+          acc = acc + (val(lo) + val(hi)) * ftaps.w[j];
         }
-      }
-      // two planes at a time: left alone, the scheduler interleaves all Z planes and the kernel comes to 339 registers
-      return true;
-    };
-    static_for_until<0, Z>(frow);
-    __builtin_amdgcn_sched_barrier(0);
+        const T qf = cvt<T>(acc);
+        buf_st<T>(qf, rf, voff, (unsigned)z * pbytes);
+        if (want_mx) strip_max<T, Z>(z, qf, keep, lane15, mx_row, smx, mx_base);
+        return true;
+      };
+      static_for_until<0, Z>(frow);
+      __builtin_amdgcn_sched_barrier(0);
+    }
   }
 
   // NI_Correlate1D's own sequence, inputs re-read (a few outputs per 10^7 on non-negative data)
@@ -239,6 +293,32 @@ __global__ __launch_bounds__(256) void gauss_axis0_folded(const T* __restrict__ 
       for (int g = 0; g < NGZ; ++g) {
         smin[((size_t)g * rows + x) * nby + yb] = fmn[g];
         sabs[((size_t)g * rows + x) * nby + yb] = fab[g];
+      }
+    }
+  }
+  // The short pass of a wave with a thread whose pairs were not exact (never on real images): from memory, in a rolled
+  // loop like the tail above, for all its lanes — the reference sequence is the definition, so that is right for every
+  // lane, and the strip maxima see all 32 stored values.  Here, behind everything else, it costs the kernel no register.
+  if constexpr (RF > 0) {
+    if (wave_bad) {
+      constexpr unsigned ZP = (Z + 15) & ~15;
+      const bool mx_row = (threadIdx.x & 16) != 0, want_mx = smx != nullptr;
+      const unsigned lane15 = threadIdx.x & 15, mx_base = (p >> 5) * ZP + lane15;
+      int keep = 0;
+#pragma unroll 1
+      for (int z = 0; z < Z; ++z) {
+        T lo[RF], hi[RF];
+#pragma unroll
+        for (int j = 1; j <= RF; ++j) {
+          lo[j - 1] = in[(size_t)border_idx(z - j, Z, IA3_MODE_REFLECT) * plane + p];
+          hi[j - 1] = in[(size_t)border_idx(z + j, Z, IA3_MODE_REFLECT) * plane + p];
+        }
+        double acc = (ld<T>(in, (size_t)z * plane + p) * 2.0) * ftaps.w[0];
+#pragma unroll
+        for (int j = RF; j >= 1; --j) acc = acc + (((double)lo[j - 1] + (double)hi[j - 1]) * 2.0) * ftaps.w[j];
+        const T qf = cvt<T>(acc);
+        fout[(size_t)z * plane + p] = qf;
+        if (want_mx) strip_max<T, Z>(z, qf, keep, lane15, mx_row, smx, mx_base);
       }
     }
   }

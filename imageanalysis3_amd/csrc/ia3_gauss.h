@@ -30,6 +30,7 @@ int column_kernel_source(bool f32, int Z);   // gauss_col_dispatch.hip: 0 none, 
 void set_column_rtc(bool on);   // IA3_TUNE_COL_RTC: may this thread's calls compile the kernels of a new depth (default: yes)
 int folded_axis0_f32(const float* src, int Z, size_t plane, const Taps& t, int mode, float* dst, hipStream_t s, int cert);
 int folded_axis0_u16(const uint16_t* src, int Z, size_t plane, const Taps& t, int mode, uint16_t* dst, hipStream_t s, int cert);
+// folded_pair_*: ft = the short filter's taps times 0.5 (gauss_col_kernel.inc)
 int folded_pair_f32(const float* src, int Z, size_t plane, const Taps& bt, float* dst, const Taps& ft, float* fdst, hipStream_t s, int cert,
                     float* smin, float* sabs, int Y, float* smx);
 int folded_pair_u16(const uint16_t* src, int Z, size_t plane, const Taps& bt, uint16_t* dst, const Taps& ft, uint16_t* fdst, hipStream_t s,

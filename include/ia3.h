@@ -59,6 +59,11 @@ int ia3_release_workspace(void);          /* drop cached device scratch buffers 
    taken from the cache), 0 = not available (the sliding-window kernels run: same results, slower), < 0 = error.  The
    reference takes any single_im_size (io_tools/load.py:166-180). */
 int ia3_prepare_depth(int dtype, int Z);
+/* The column kernel's host side, for its tests (no device needed).  ia3_col_guard: the default guard distance (f64 ulps)
+   of its certificate for a stack depth, a radius and a border mode.  ia3_col_weights: its weight stream for the taps
+   w[0 .. R] (csrc/ia3_col_weights.h); writes at most cap doubles and returns the stream's length. */
+int ia3_col_guard(int Z, int R, int mode);
+int ia3_col_weights(int Z, int R, int mode, const double* taps, double* out, int cap);
 /* the scratch cache: out6 = {idle bytes, bytes in use, blocks, hipMalloc calls, hipFree calls, ms spent in both} since
    the library was loaded; a steady-state loop adds no calls (each hipFree synchronises the device) */
 int ia3_workspace_stats(double* out6);
