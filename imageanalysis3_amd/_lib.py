@@ -45,6 +45,8 @@ EXPORTS = [
     "ia3_label_boxes_dev", "ia3_cube_labels_dev", "ia3_cube_max_dev", "ia3_cube_gather_dev",
     "ia3_plane_medians_dev", "ia3_chrom_seed_mask_dev", "ia3_binary_morph_dev", "ia3_binary_fill_holes_dev", "ia3_label_dev",
     "ia3_label_centers_dev", "ia3_remove_small_labels_dev", "ia3_find_candidate_chromosomes_dev",
+    "ia3_chrom_image_create", "ia3_chrom_image_free", "ia3_chrom_image_upload", "ia3_chrom_image_download",
+    "ia3_chrom_image_add_dev", "ia3_stack_median_dev", "ia3_find_candidate_chromosomes_f64_dev",
 ]
 
 
@@ -143,6 +145,7 @@ def lib():
         L.ia3_stack_free.restype = None
         L.ia3_fit_destroy.restype = None
         L.ia3_drift_ref_free.restype = None
+        L.ia3_chrom_image_free.restype = None
         _lib = L
     return _lib
 
@@ -606,18 +609,108 @@ def remove_small_labels(labels, max_label, min_size):
     return out
 
 
+CHROM_ADD_BATCH = 16   # images of one launch of ia3_chrom_image_add_dev
+
+
+def stack_median(stack):
+    """``ia3_stack_median_dev``: ``np.median`` of a whole resident stack, as ``np.float64``."""
+    out = C.c_double(0)
+    check(lib().ia3_stack_median_dev(stack._h, C.byref(out)))
+    return np.float64(out.value)
+
+
+class ChromImage(object):
+    """A float64 (Z, X, Y) volume resident in HBM (owner of an ``ia3_chrom_image`` handle): the chromosome image that
+    ``Field_of_View._generate_chrom_im_from_data`` sums up, and what ``find_candidate_chromosomes`` reads in float64."""
+
+    def __init__(self, handle, shape):
+        self._h = handle
+        self.shape = tuple(int(v) for v in shape)
+        self.dtype = np.dtype(np.float64)
+
+    @classmethod
+    def empty(cls, shape):
+        """``np.zeros(shape)`` on the device."""
+        shape = tuple(int(v) for v in shape)
+        if len(shape) != 3:
+            raise IndexError("a 3-D (z,x,y) shape is required, got %s" % (shape,))
+        h = C.c_void_p()
+        check(lib().ia3_chrom_image_create(shape[0], shape[1], shape[2], C.byref(h)))
+        return cls(h, shape)
+
+    @classmethod
+    def upload(cls, im):
+        """A resident copy of a float64 (z, x, y) ndarray (values are not converted: the array must be float64)."""
+        if not isinstance(im, np.ndarray):
+            raise TypeError("image given should be a numpy.ndarray, but %s is given." % type(im))
+        if im.dtype != np.float64:
+            raise TypeError("a chromosome image is float64, got %s" % im.dtype)
+        if im.ndim != 3:
+            raise IndexError("a 3-D (z,x,y) stack is required, got ndim=%d" % im.ndim)
+        a = np.ascontiguousarray(im)
+        out = cls.empty(a.shape)
+        try:
+            check(lib().ia3_chrom_image_upload(out._h, dptr(a)))
+        except Exception:
+            out.free()
+            raise
+        return out
+
+    def download(self):
+        out = np.empty(self.shape, dtype=np.float64)
+        check(lib().ia3_chrom_image_download(self._h, dptr(out)))
+        return out
+
+    def add(self, stacks, flags, shifts):
+        """``ia3_chrom_image_add_dev``: add the resident uint16 ``stacks``; ``flags[k] == 2``: as it is, otherwise moved by
+        the integer ``shifts[k]`` (z, x, y: out[j] += im[j + shift]) and filled up with its median.  Returns the medians
+        used (0 for a flag-2 image) as a float64 array."""
+        stacks = list(stacks)
+        n = len(stacks)
+        fl = np.ascontiguousarray(flags, dtype=np.int32).ravel()
+        sh = np.ascontiguousarray(shifts, dtype=np.int32).reshape(-1, 3) if n else np.zeros((0, 3), np.int32)
+        if len(fl) != n or len(sh) != n:
+            raise ValueError("ChromImage.add: %d stacks, %d flags, %d shifts" % (n, len(fl), len(sh)))
+        bg = np.zeros(n, dtype=np.float64)
+        if n == 0:
+            return bg
+        hs = (C.c_void_p * n)(*[s._h for s in stacks])
+        check(lib().ia3_chrom_image_add_dev(self._h, hs, fl.ctypes.data_as(C.POINTER(C.c_int)),
+                                            sh.ctypes.data_as(C.POINTER(C.c_int)), n, dptr(bg)))
+        return bg
+
+    def free(self):
+        if self._h is not None:
+            lib().ia3_chrom_image_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
 def find_candidate_chromosomes(stack, filt_size, binary_per_th, morphology_size, min_label_size, return_label=False,
                                capacity=4096):
-    """``ia3_find_candidate_chromosomes_dev`` on a resident stack: ((n, 3) float64 centres, threshold as ``np.float64``,
-    resident uint16 kept-label stack or None)."""
+    """``ia3_find_candidate_chromosomes_dev`` on a resident stack, ``ia3_find_candidate_chromosomes_f64_dev`` on a
+    ``ChromImage``: ((n, 3) float64 centres, threshold as ``np.float64``, resident uint16 kept-label stack or None)."""
     p = ChromParams(int(filt_size), int(morphology_size), int(min_label_size), float(binary_per_th))
     kept = DeviceStack.empty(stack.shape, np.uint16) if return_label else None
+    entry = (lib().ia3_find_candidate_chromosomes_f64_dev if isinstance(stack, ChromImage)
+             else lib().ia3_find_candidate_chromosomes_dev)
     n, th = C.c_int(0), C.c_double(0)
     try:
         while True:
             coords = np.empty((capacity, 3), dtype=np.float64)
-            rc = lib().ia3_find_candidate_chromosomes_dev(stack._h, C.byref(p), dptr(coords), int(capacity), C.byref(n),
-                                                          C.byref(th), None if kept is None else kept._h)
+            rc = entry(stack._h, C.byref(p), dptr(coords), int(capacity), C.byref(n),
+                       C.byref(th), None if kept is None else kept._h)
             if rc == IA3_ECAPACITY and n.value > capacity:
                 capacity = n.value
                 continue

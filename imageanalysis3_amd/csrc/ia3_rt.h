@@ -16,6 +16,14 @@ struct ia3_stack {
   void* home = nullptr;   // hipStream_t of the thread that allocated it (owned stacks): see ia3_stack_free
 };
 
+// float64 (Z,X,Y) volume in a library allocation: the chromosome image (chromim.hip writes it, morph.hip reads it)
+struct ia3_chrom_image {
+  ia3_stack* store;   // owner of the memory: a (2 Z, X, Y) float32 stack of the library, so it is cached and freed like one
+  double* d;
+  int Z, X, Y;
+  size_t n;           // voxels
+};
+
 namespace ia3rt {
 
 int set_error(int code, const char* fmt, ...);

@@ -1,9 +1,9 @@
 // Candidate chromosomes from a resident stack (reference: segmentation_tools/chromosome.py:264-361
 // find_candidate_chromosomes) and the operators it is made of:
-//   seg_hist_k / seg_pick_k   exact order statistics per plane or of a whole volume (radix select, 8 key bits per pass;
+//   ia3_select.h              exact order statistics per plane or of a whole volume (radix select, 8 key bits per pass;
 //                             uint16, float32 and float64 keys): np.median of every plane, scoreatpercentile of the seed
 //   range_k                   maximum_filter - minimum_filter of lyr / np.median(lyr), mode 'nearest', in the image's
-//                             arithmetic (uint16: float64, float32: float32)
+//                             arithmetic (uint16 and float64: float64, float32: float32)
 //   mask_k                    seed > threshold with the edges cleared, one bit per voxel
 //   morph_k                   binary erosion / dilation by ball(r) on bit rows (shifts, ANDs and ORs of words)
 //   ccl_*_k                   6-connected labelling: union-find inside an LDS tile, atomicMin unions across tile faces,
@@ -14,6 +14,7 @@
 // rounded), so results equal NumPy / SciPy bit for bit and are the same on every run.  The shared arithmetic is
 // csrc/ia3_ccl.h, which tests/native/ccl_cpu.cpp builds for the host.
 #include "ia3_rt.h"
+#include "ia3_select.h"
 #include "ia3_ccl.h"
 #include <limits.h>
 #include <math.h>
@@ -25,175 +26,6 @@ using namespace ia3rt;
 namespace {
 using namespace ia3ccl;
 
-typedef unsigned long long u64;
-
-// ---- order-preserving keys ---------------------------------------------------------------------------------------------------
-// NaNs of either sign order last, as np.sort puts them
-template <class T> struct KeyOf;
-template <> struct KeyOf<uint16_t> {
-  static constexpr int BITS = 16;
-  static __host__ __device__ inline u64 key(uint16_t v) { return v; }
-};
-template <> struct KeyOf<float> {
-  static constexpr int BITS = 32;
-  static __host__ __device__ inline u64 key(float v) {
-    if (v != v) return 0xFFFFFFFFull;
-    uint32_t b;
-    memcpy(&b, &v, 4);
-    return b & 0x80000000u ? (uint32_t)~b : (b | 0x80000000u);
-  }
-};
-template <> struct KeyOf<double> {
-  static constexpr int BITS = 64;
-  static __host__ __device__ inline u64 key(double v) {
-    if (v != v) return ~0ull;
-    u64 b;
-    memcpy(&b, &v, 8);
-    return b >> 63 ? ~b : (b | (1ull << 63));
-  }
-};
-float key_to_f32(u64 k) {
-  uint32_t b = (uint32_t)k;
-  b = b & 0x80000000u ? (b & 0x7FFFFFFFu) : ~b;
-  float v;
-  memcpy(&v, &b, 4);
-  return v;
-}
-double key_to_f64(u64 k) {
-  k = k >> 63 ? (k & ~(1ull << 63)) : ~k;
-  double v;
-  memcpy(&v, &k, 8);
-  return v;
-}
-
-// ---- segmented radix select: two ranks in each of S equally long segments ---------------------------------------------------
-struct SelSeg {
-  u64 k[2];        // rank still to find among the values that share prefix[r]
-  u64 prefix[2];   // key bits decided so far (high bits)
-  unsigned nan;    // the segment holds a NaN
-  unsigned pad;
-};
-constexpr int NB = 256;
-
-__device__ __forceinline__ bool same_prefix(const SelSeg& s, int pass, int shift) {
-  return pass == 0 || (s.prefix[0] >> (shift + 8)) == (s.prefix[1] >> (shift + 8));
-}
-
-// histogram of digit `pass` of the values of segment blockIdx.y whose higher digits equal a rank's prefix; the two ranks
-// share one histogram while their prefixes agree.  hist: S x 2 x NB, zero before the launch.
-template <class T>
-__global__ __launch_bounds__(256) void seg_hist_k(const T* __restrict__ v, size_t seglen, int pass, SelSeg* __restrict__ st,
-                                                  unsigned* __restrict__ hist) {
-  __shared__ unsigned h[2 * NB];
-  const int seg = blockIdx.y;
-  const int shift = KeyOf<T>::BITS - 8 * (pass + 1);
-  const SelSeg s = st[seg];
-  const bool same = same_prefix(s, pass, shift);
-  const u64 p0 = pass == 0 ? 0 : s.prefix[0] >> (shift + 8), p1 = pass == 0 ? 0 : s.prefix[1] >> (shift + 8);
-  for (int i = threadIdx.x; i < 2 * NB; i += 256) h[i] = 0;
-  __syncthreads();
-  const T* p = v + (size_t)seg * seglen;
-  bool nan = false;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < seglen; i += (size_t)gridDim.x * 256) {
-    const T e = p[i];
-    if (pass == 0 && e != e) nan = true;
-    const u64 key = KeyOf<T>::key(e);
-    const unsigned d = (unsigned)(key >> shift) & (NB - 1);
-    const u64 hi = pass == 0 ? 0 : key >> (shift + 8);
-    if (hi == p0) atomicAdd(&h[d], 1u);
-    if (!same && hi == p1) atomicAdd(&h[NB + d], 1u);
-  }
-  if (nan) atomicOr(&st[seg].nan, 1u);
-  __syncthreads();
-  unsigned* out = hist + (size_t)seg * 2 * NB;
-  for (int i = threadIdx.x; i < 2 * NB; i += 256)
-    if (h[i]) atomicAdd(&out[i], h[i]);
-}
-
-// one thread per segment: each rank moves into the bucket that holds it
-__global__ void seg_pick_k(SelSeg* __restrict__ st, const unsigned* __restrict__ hist, int S, int pass, int bits) {
-  const int seg = blockIdx.x * blockDim.x + threadIdx.x;
-  if (seg >= S) return;
-  const int shift = bits - 8 * (pass + 1);
-  SelSeg s = st[seg];
-  const bool same = same_prefix(s, pass, shift);
-  for (int r = 0; r < 2; ++r) {
-    const unsigned* h = hist + ((size_t)seg * 2 + (r == 1 && !same ? 1 : 0)) * NB;
-    u64 k = s.k[r], cum = 0;
-    int b = 0;
-    for (; b < NB; ++b) {
-      const u64 c = h[b];
-      if (cum + c > k) break;
-      cum += c;
-    }
-    if (b >= NB) b = NB - 1;
-    st[seg].prefix[r] = s.prefix[r] | ((u64)b << shift);
-    st[seg].k[r] = k - cum;
-  }
-}
-
-// keys of the order statistics k0 <= k1 of every segment (host: 2 per segment) and the NaN flags
-template <class T>
-int seg_select(const T* dev, int S, size_t seglen, u64 k0, u64 k1, std::vector<u64>& keys, std::vector<unsigned>& nan) {
-  hipStream_t st = stream();
-  std::vector<SelSeg> h((size_t)S);
-  for (auto& s : h) { s.k[0] = k0; s.k[1] = k1; s.prefix[0] = s.prefix[1] = 0; s.nan = 0; s.pad = 0; }
-  const size_t hist_bytes = (size_t)S * 2 * NB * sizeof(unsigned);
-  Scratch dst((size_t)S * sizeof(SelSeg)), dh(hist_bytes);
-  if (!dst.p || !dh.p) return set_error(IA3_ENOMEM, "scratch of the order statistics");
-  IA3_HIP(hipMemcpyAsync(dst.p, h.data(), (size_t)S * sizeof(SelSeg), hipMemcpyHostToDevice, st));
-  IA3_HIP(hipStreamSynchronize(st));   // h is pageable
-  const size_t per_block = 256 * 32;
-  size_t want = (seglen + per_block - 1) / per_block;
-  size_t gmax = (size_t)num_cus() * 8 / (size_t)S;
-  if (gmax < 1) gmax = 1;
-  if (want > gmax) want = gmax;
-  if (want < 1) want = 1;
-  const int passes = KeyOf<T>::BITS / 8;
-  {
-    ProfScope ps("morph_select");
-    for (int pass = 0; pass < passes; ++pass) {
-      IA3_HIP(hipMemsetAsync(dh.p, 0, hist_bytes, st));
-      hipLaunchKernelGGL((seg_hist_k<T>), dim3((unsigned)want, (unsigned)S), dim3(256), 0, st, dev, seglen, pass, dst.as<SelSeg>(),
-                         dh.as<unsigned>());
-      hipLaunchKernelGGL(seg_pick_k, dim3((unsigned)((S + 63) / 64)), dim3(64), 0, st, dst.as<SelSeg>(), (const unsigned*)dh.p, S,
-                         pass, KeyOf<T>::BITS);
-    }
-    IA3_KCHECK();
-  }
-  IA3_HIP(hipMemcpyAsync(h.data(), dst.p, (size_t)S * sizeof(SelSeg), hipMemcpyDeviceToHost, st));
-  IA3_HIP(hipStreamSynchronize(st));
-  keys.resize((size_t)S * 2);
-  nan.resize((size_t)S);
-  for (int i = 0; i < S; ++i) { keys[2 * i] = h[i].prefix[0]; keys[2 * i + 1] = h[i].prefix[1]; nan[i] = h[i].nan; }
-  return IA3_OK;
-}
-
-// np.median of every plane as the reference's division sees it: float64 for a uint16 stack, float32 for a float32 one
-// (chromosome.py:296); med64 holds the value widened to float64 either way
-int plane_medians(const ia3_stack* s, std::vector<double>& med64) {
-  const size_t plane = (size_t)s->X * s->Y;
-  const u64 k0 = (plane - 1) / 2, k1 = plane / 2;   // the middle value twice (odd count) or the two middle values
-  std::vector<u64> keys;
-  std::vector<unsigned> nan;
-  int rc = s->dtype == IA3_F32 ? seg_select<float>((const float*)s->d, s->Z, plane, k0, k1, keys, nan)
-                               : seg_select<uint16_t>((const uint16_t*)s->d, s->Z, plane, k0, k1, keys, nan);
-  if (rc) return rc;
-  med64.resize((size_t)s->Z);
-  for (int z = 0; z < s->Z; ++z) {
-    if (s->dtype == IA3_F32) {
-      const float a = key_to_f32(keys[2 * z]), b = key_to_f32(keys[2 * z + 1]);
-      volatile float sum = a + b;                       // np.mean of the two float32 values: added, then halved, in float32
-      const float m = k0 == k1 ? a : sum / 2.0f;
-      med64[z] = nan[z] ? (double)NAN : (double)m;
-    } else {
-      const double a = (double)keys[2 * z], b = (double)keys[2 * z + 1];
-      med64[z] = k0 == k1 ? a : (a + b) / 2.0;
-    }
-  }
-  return IA3_OK;
-}
-
 // ---- range filter ------------------------------------------------------------------------------------------------------------
 constexpr int RZ = 4, RX = 8, RY = 32;         // outputs of a block
 constexpr int RH = 4;                          // largest halo (filter size 5)
@@ -201,6 +33,7 @@ constexpr int RLX = RX + RH, RLY = RY + RH;    // LDS tile pitches
 
 __device__ __forceinline__ double quotient(uint16_t v, double m) { return (double)v / m; }   // IEEE division
 __device__ __forceinline__ float quotient(float v, float m) { return __fdiv_rn(v, m); }
+__device__ __forceinline__ double quotient(double v, double m) { return v / m; }             // IEEE division
 
 // out = max - min over the s^3 window (offsets window_lo(s) .. window_hi(s), indices clamped) of im[z] / med[z].  The
 // tile with its clamped halo is divided once while it is staged in LDS.
@@ -517,15 +350,19 @@ struct Dims {
   size_t nwords;
 };
 
-int dims_of(const ia3_stack* s, Dims& d) {
-  if (!s || !s->d) return set_error(IA3_EINVAL, "null stack");
-  if (s->Z < 1 || s->X < 1 || s->Y < 1) return set_error(IA3_EINVAL, "empty stack");
-  const size_t nvox = (size_t)s->Z * s->X * s->Y;
+int dims_of(const void* dev, int Z, int X, int Y, Dims& d) {
+  if (!dev) return set_error(IA3_EINVAL, "null stack");
+  if (Z < 1 || X < 1 || Y < 1) return set_error(IA3_EINVAL, "empty stack");
+  const size_t nvox = (size_t)Z * X * Y;
   if (nvox > (size_t)INT_MAX) return set_error(IA3_EUNSUPPORTED, "stacks of up to 2^31 - 1 voxels are labelled (int32 parents and labels)");
-  d.Z = s->Z; d.X = s->X; d.Y = s->Y; d.W = words_per_row(s->Y);
+  d.Z = Z; d.X = X; d.Y = Y; d.W = words_per_row(Y);
   d.n = (unsigned)nvox;
-  d.nwords = (size_t)s->Z * s->X * d.W;
+  d.nwords = (size_t)Z * X * d.W;
   return IA3_OK;
+}
+int dims_of(const ia3_stack* s, Dims& d) {
+  if (!s) return set_error(IA3_EINVAL, "null stack");
+  return dims_of(s->d, s->Z, s->X, s->Y, d);
 }
 
 int check_mask(const ia3_stack* m, Dims& d) {
@@ -653,10 +490,11 @@ int upload_map(const std::vector<int>& map, Scratch& dmap) {
   return IA3_OK;
 }
 
-// seed image of chromosome.py:296-299 into `seed` (float64 for a uint16 stack, float32 for a float32 one)
-int range_image(const ia3_stack* s, const Dims& d, const std::vector<double>& med64, int fs, void* seed) {
+// seed image of chromosome.py:296-299 into `seed` (float32 for a float32 stack, float64 for a uint16 stack and for a
+// float64 volume)
+int range_image(const void* im, int kind, const Dims& d, const std::vector<double>& med64, int fs, void* seed) {
   hipStream_t st = stream();
-  const bool f32 = s->dtype == IA3_F32;
+  const bool f32 = kind == IA3_F32;
   Scratch dmed((size_t)d.Z * sizeof(double));
   if (!dmed.p) return set_error(IA3_ENOMEM, "plane medians");
   std::vector<float> med32;
@@ -670,8 +508,9 @@ int range_image(const ia3_stack* s, const Dims& d, const std::vector<double>& me
   IA3_HIP(hipStreamSynchronize(st));
   ProfScope ps("morph_range");
   const dim3 grid(tiles(d.Y, RY), tiles(d.X, RX), tiles(d.Z, RZ));
-  if (f32) hipLaunchKernelGGL((range_k<float, float>), grid, dim3(256), 0, st, (const float*)s->d, d.Z, d.X, d.Y, (const float*)dmed.p, fs, (float*)seed);
-  else hipLaunchKernelGGL((range_k<uint16_t, double>), grid, dim3(256), 0, st, (const uint16_t*)s->d, d.Z, d.X, d.Y, (const double*)dmed.p, fs, (double*)seed);
+  if (f32) hipLaunchKernelGGL((range_k<float, float>), grid, dim3(256), 0, st, (const float*)im, d.Z, d.X, d.Y, (const float*)dmed.p, fs, (float*)seed);
+  else if (kind == IA3_SEL_F64) hipLaunchKernelGGL((range_k<double, double>), grid, dim3(256), 0, st, (const double*)im, d.Z, d.X, d.Y, (const double*)dmed.p, fs, (double*)seed);
+  else hipLaunchKernelGGL((range_k<uint16_t, double>), grid, dim3(256), 0, st, (const uint16_t*)im, d.Z, d.X, d.Y, (const double*)dmed.p, fs, (double*)seed);
   IA3_KCHECK();
   return IA3_OK;
 }
@@ -707,16 +546,17 @@ int check_seed_args(int filt_size, double per) {
 }
 
 // steps 1-2 of find_candidate_chromosomes (chromosome.py:293-311): the thresholded, edge-cleared mask as bits
-int seed_mask_bits(const ia3_stack* im, const Dims& d, int filt_size, double per, u64* bits, double* threshold) {
+int seed_mask_bits(const void* im, int kind, const Dims& d, int filt_size, double per, u64* bits, double* threshold) {
   std::vector<double> med;
-  int rc = plane_medians(im, med); if (rc) return rc;
+  // np.median of every plane as the reference's division sees it (chromosome.py:296), widened to float64
+  int rc = segment_medians(im, kind, d.Z, (size_t)d.X * d.Y, med); if (rc) return rc;
   for (int z = 0; z < d.Z; ++z)
     if (!(med[z] != 0) || !isfinite(med[z]))
       return set_error(IA3_EINVAL, "plane %d has the median %g: the layer adjustment divides by it", z, med[z]);
-  const bool f32 = im->dtype == IA3_F32;
+  const bool f32 = kind == IA3_F32;
   Scratch seed((size_t)d.n * (f32 ? sizeof(float) : sizeof(double)));
   if (!seed.p) return set_error(IA3_ENOMEM, "seed image of %u voxels", d.n);
-  rc = range_image(im, d, med, filt_size, seed.p); if (rc) return rc;
+  rc = range_image(im, kind, d, med, filt_size, seed.p); if (rc) return rc;
   rc = f32 ? percentile_of<float>(seed.as<float>(), d.n, per, threshold) : percentile_of<double>(seed.as<double>(), d.n, per, threshold);
   if (rc) return rc;
   ProfScope ps("morph_mask");
@@ -725,6 +565,57 @@ int seed_mask_bits(const ia3_stack* im, const Dims& d, int filt_size, double per
   else hipLaunchKernelGGL((mask_k<double>), dim3(blocks_of(d.nwords, 4)), dim3(256), 0, stream(), (const double*)seed.p, d.Z, d.X, d.Y, d.W, *threshold, e, bits, d.nwords);
   IA3_KCHECK();
   IA3_HIP(hipStreamSynchronize(stream()));   // `seed` goes back to the cache
+  return IA3_OK;
+}
+
+// find_candidate_chromosomes (chromosome.py:264-361) of a resident uint16 / float32 stack or float64 volume
+int candidate_chromosomes(const void* im, int kind, const Dims& d, const ia3_chrom_params* p, double* coords_zxy, int capacity,
+                          int* n_out, double* threshold, ia3_stack* kept_labels) {
+  if (!p || !n_out || !threshold) return set_error(IA3_EINVAL, "null argument");
+  int rc = check_seed_args(p->filt_size, p->binary_per_th); if (rc) return rc;
+  if (p->morphology_size != 1)
+    return set_error(IA3_EUNSUPPORTED, "_morphology_size %d: the fused entry is built for ball(1), where a hole is a 6-connected background component; compose the operators for other sizes", p->morphology_size);
+  if (capacity < 0 || (capacity > 0 && !coords_zxy)) return set_error(IA3_EINVAL, "bad coordinate table");
+  if (kept_labels) { rc = same_shape_u16(kept_labels, d, "kept-label stack"); if (rc) return rc; }
+  *n_out = 0;
+  Scratch a(d.nwords * sizeof(u64)), b(d.nwords * sizeof(u64));
+  if (!a.p || !b.p) return set_error(IA3_ENOMEM, "mask bits");
+  u64 *A = a.as<u64>(), *B = b.as<u64>();
+  rc = seed_mask_bits(im, kind, d, p->filt_size, p->binary_per_th, A, threshold); if (rc) return rc;
+  // chromosome.py:317-319: opening by ball(1) (outside counts as clear for both halves), holes filled
+  rc = morph(A, d, 1, 0, 0, B); if (rc) return rc;
+  rc = morph(B, d, 1, 1, 0, A); if (rc) return rc;
+  rc = fill_holes(A, d, B); if (rc) return rc;
+  // :323-324: opening by ball(0) is the identity; closing by ball(1) (DESIGN.md §19: its border rule cannot matter here)
+  rc = morph(B, d, 1, 1, 0, A); if (rc) return rc;
+  rc = morph(A, d, 1, 0, 1, B); if (rc) return rc;
+  // :325-337: label; the random walker returns fully labelled input as it is; small labels go
+  Scratch parent((size_t)d.n * sizeof(int)), lab((size_t)d.n * sizeof(int));
+  if (!parent.p || !lab.p) return set_error(IA3_ENOMEM, "scratch of the labelling");
+  int n = 0;
+  rc = label_bits(B, d, parent.as<int>(), lab.as<int>(), &n); if (rc) return rc;
+  if (n > 65535) return set_error(IA3_EUNSUPPORTED, "%d components do not fit the reference's uint16 labels (it wraps silently)", n);
+  std::vector<int> map((size_t)n + 1, 0);
+  int kept = 0;
+  std::vector<u64> table;
+  if (n > 0) {
+    rc = label_sums(lab.p, 32, d.n, d.X, d.Y, n, table); if (rc) return rc;
+    for (int l = 1; l <= n; ++l)
+      if ((long long)table[(size_t)l * 7] >= (long long)p->min_label_size) { map[l] = l; ++kept; }
+  }
+  if (kept_labels) {
+    Scratch dmap(map.size() * sizeof(int));
+    if (!dmap.p) return set_error(IA3_ENOMEM, "label map");
+    rc = upload_map(map, dmap); if (rc) return rc;
+    hipLaunchKernelGGL((label_map_u16_k<int>), dim3(blocks_of(d.n, 256)), dim3(256), 0, stream(), (const int*)lab.p, d.n, n, (const int*)dmap.p, (uint16_t*)kept_labels->d);
+    IA3_KCHECK();
+    IA3_HIP(hipStreamSynchronize(stream()));
+  }
+  *n_out = kept;
+  if (kept > capacity) return set_error(IA3_ECAPACITY, "%d candidate chromosomes, room for %d", kept, capacity);
+  int row = 0;
+  for (int l = 1; l <= n; ++l)
+    if (map[l]) centre_of(&table[(size_t)l * 7], coords_zxy + 3 * (size_t)row++);
   return IA3_OK;
 }
 
@@ -738,7 +629,7 @@ int ia3_plane_medians_dev(const ia3_stack* s, double* out) {
   rc = check_image(s, d); if (rc) return rc;
   if (!out) return set_error(IA3_EINVAL, "null output");
   std::vector<double> med;
-  rc = plane_medians(s, med); if (rc) return rc;
+  rc = segment_medians(s->d, s->dtype, d.Z, (size_t)d.X * d.Y, med); if (rc) return rc;
   memcpy(out, med.data(), (size_t)d.Z * sizeof(double));
   return IA3_OK;
 }
@@ -752,7 +643,7 @@ int ia3_chrom_seed_mask_dev(const ia3_stack* im, int filt_size, double binary_pe
   rc = same_shape_u16(mask_out, d, "mask"); if (rc) return rc;
   Scratch bits(d.nwords * sizeof(u64));
   if (!bits.p) return set_error(IA3_ENOMEM, "mask bits");
-  rc = seed_mask_bits(im, d, filt_size, binary_per_th, bits.as<u64>(), threshold); if (rc) return rc;
+  rc = seed_mask_bits(im->d, im->dtype, d, filt_size, binary_per_th, bits.as<u64>(), threshold); if (rc) return rc;
   return unpack_mask(bits.as<u64>(), d, mask_out);
 }
 
@@ -847,52 +738,16 @@ int ia3_find_candidate_chromosomes_dev(const ia3_stack* im, const ia3_chrom_para
   int rc = ensure_init(); if (rc) return rc;
   Dims d;
   rc = check_image(im, d); if (rc) return rc;
-  if (!p || !n_out || !threshold) return set_error(IA3_EINVAL, "null argument");
-  rc = check_seed_args(p->filt_size, p->binary_per_th); if (rc) return rc;
-  if (p->morphology_size != 1)
-    return set_error(IA3_EUNSUPPORTED, "_morphology_size %d: the fused entry is built for ball(1), where a hole is a 6-connected background component; compose the operators for other sizes", p->morphology_size);
-  if (capacity < 0 || (capacity > 0 && !coords_zxy)) return set_error(IA3_EINVAL, "bad coordinate table");
-  if (kept_labels) { rc = same_shape_u16(kept_labels, d, "kept-label stack"); if (rc) return rc; }
-  *n_out = 0;
-  Scratch a(d.nwords * sizeof(u64)), b(d.nwords * sizeof(u64));
-  if (!a.p || !b.p) return set_error(IA3_ENOMEM, "mask bits");
-  u64 *A = a.as<u64>(), *B = b.as<u64>();
-  rc = seed_mask_bits(im, d, p->filt_size, p->binary_per_th, A, threshold); if (rc) return rc;
-  // chromosome.py:317-319: opening by ball(1) (outside counts as clear for both halves), holes filled
-  rc = morph(A, d, 1, 0, 0, B); if (rc) return rc;
-  rc = morph(B, d, 1, 1, 0, A); if (rc) return rc;
-  rc = fill_holes(A, d, B); if (rc) return rc;
-  // :323-324: opening by ball(0) is the identity; closing by ball(1) (DESIGN.md §19: its border rule cannot matter here)
-  rc = morph(B, d, 1, 1, 0, A); if (rc) return rc;
-  rc = morph(A, d, 1, 0, 1, B); if (rc) return rc;
-  // :325-337: label; the random walker returns fully labelled input as it is; small labels go
-  Scratch parent((size_t)d.n * sizeof(int)), lab((size_t)d.n * sizeof(int));
-  if (!parent.p || !lab.p) return set_error(IA3_ENOMEM, "scratch of the labelling");
-  int n = 0;
-  rc = label_bits(B, d, parent.as<int>(), lab.as<int>(), &n); if (rc) return rc;
-  if (n > 65535) return set_error(IA3_EUNSUPPORTED, "%d components do not fit the reference's uint16 labels (it wraps silently)", n);
-  std::vector<int> map((size_t)n + 1, 0);
-  int kept = 0;
-  std::vector<u64> table;
-  if (n > 0) {
-    rc = label_sums(lab.p, 32, d.n, d.X, d.Y, n, table); if (rc) return rc;
-    for (int l = 1; l <= n; ++l)
-      if ((long long)table[(size_t)l * 7] >= (long long)p->min_label_size) { map[l] = l; ++kept; }
-  }
-  if (kept_labels) {
-    Scratch dmap(map.size() * sizeof(int));
-    if (!dmap.p) return set_error(IA3_ENOMEM, "label map");
-    rc = upload_map(map, dmap); if (rc) return rc;
-    hipLaunchKernelGGL((label_map_u16_k<int>), dim3(blocks_of(d.n, 256)), dim3(256), 0, stream(), (const int*)lab.p, d.n, n, (const int*)dmap.p, (uint16_t*)kept_labels->d);
-    IA3_KCHECK();
-    IA3_HIP(hipStreamSynchronize(stream()));
-  }
-  *n_out = kept;
-  if (kept > capacity) return set_error(IA3_ECAPACITY, "%d candidate chromosomes, room for %d", kept, capacity);
-  int row = 0;
-  for (int l = 1; l <= n; ++l)
-    if (map[l]) centre_of(&table[(size_t)l * 7], coords_zxy + 3 * (size_t)row++);
-  return IA3_OK;
+  return candidate_chromosomes(im->d, im->dtype, d, p, coords_zxy, capacity, n_out, threshold, kept_labels);
+}
+
+int ia3_find_candidate_chromosomes_f64_dev(const ia3_chrom_image* im, const ia3_chrom_params* p, double* coords_zxy, int capacity,
+                                           int* n_out, double* threshold, ia3_stack* kept_labels) {
+  int rc = ensure_init(); if (rc) return rc;
+  if (!im) return set_error(IA3_EINVAL, "null chromosome image");
+  Dims d;
+  rc = dims_of(im->d, im->Z, im->X, im->Y, d); if (rc) return rc;
+  return candidate_chromosomes(im->d, IA3_SEL_F64, d, p, coords_zxy, capacity, n_out, threshold, kept_labels);
 }
 
 }  // extern "C"

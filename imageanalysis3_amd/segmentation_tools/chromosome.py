@@ -17,8 +17,9 @@ _COMPOSE = ("compose it from segmentation_tools.morphology (ball, binary_erosion
 
 
 def _image_form(_chrom_im):
-    """What goes to the device for ``_chrom_im``: the resident stack itself, or a uint16 / float32 ndarray."""
-    if isinstance(_chrom_im, L.DeviceStack):
+    """What goes to the device for ``_chrom_im``: the resident stack or chromosome image itself, or a uint16 / float32
+    ndarray."""
+    if isinstance(_chrom_im, (L.DeviceStack, L.ChromImage)):
         return _chrom_im
     a = np.asarray(_chrom_im)
     if a.ndim != 3:
@@ -53,7 +54,10 @@ def find_candidate_chromosomes(_chrom_im,
                                _return_label=False):
     """segmentation_tools/chromosome.py:264-361 — centres (z, x, y pixels, (n, 3) float64, ``np.array([])`` when there is
     no object) of the candidate chromosomes of ``_chrom_im``: a uint16 / float32 ndarray or a resident ``DeviceStack``
-    (never downloaded); a float64 ndarray only when every value is exact in float32.
+    (never downloaded); a float64 ndarray only when every value is exact in float32.  A resident ``ChromImage`` (what
+    ``classes.field_of_view.generate_chrom_im`` returns with ``return_device=True``, or ``ChromImage.upload`` of a
+    float64 ndarray) is processed in float64, as the reference processes a float64 image: float64 plane medians, quotients
+    and seed.
 
     ``_adjust_layers``, ``_random_walk_beta`` and ``_num_threads`` have no effect: the reference ignores the first, its
     random walker returns the labels it was given (none of them is 0, :326), and no process pool is started here.
@@ -66,7 +70,7 @@ def find_candidate_chromosomes(_chrom_im,
         raise NotImplementedError("_morphology_size %s: only ball(1) is built into the fused call (with a larger ball "
                                   "hole filling is no longer plain connectivity); %s" % (_morphology_size, _COMPOSE))
     form = _image_form(_chrom_im)
-    own = not isinstance(form, L.DeviceStack)
+    own = not isinstance(form, (L.DeviceStack, L.ChromImage))
     if own:
         _check_medians(form)
     if _verbose:

@@ -670,6 +670,34 @@ typedef struct ia3_chrom_params {
 int ia3_find_candidate_chromosomes_dev(const ia3_stack* im, const ia3_chrom_params* p, double* coords_zxy, int capacity,
                                        int* n_out, double* threshold, ia3_stack* kept_labels);
 
+/* ---- the chromosome image (chromim.hip) ----------------------------------------------------------------
+ * classes/field_of_view.py:1821-1917 Field_of_View._generate_chrom_im_from_data: the float64 sum of every processed
+ * round of a field of view, and find_candidate_chromosomes on it in the reference's float64 arithmetic.
+ * An ia3_chrom_image is a float64 (Z,X,Y) volume in device memory; create gives zeros (np.zeros(single_im_size)),
+ * upload / download copy the whole volume from / to Z * X * Y host doubles. */
+typedef struct ia3_chrom_image ia3_chrom_image;
+int ia3_chrom_image_create(int Z, int X, int Y, ia3_chrom_image** out);
+void ia3_chrom_image_free(ia3_chrom_image* h);
+int ia3_chrom_image_upload(ia3_chrom_image* h, const double* host);
+int ia3_chrom_image_download(const ia3_chrom_image* h, double* host);
+/* np.median of a whole resident stack, widened to float64: the middle order statistic, or for an even count the mean of
+ * the two middle ones (uint16: in float64; float32: added and halved in float32).  NaN when the stack holds one. */
+int ia3_stack_median_dev(const ia3_stack* s, double* out);
+/* :1869-1891 (_fast): h += every one of the n resident uint16 stacks ims[k] of h's shape.  flags[k] == 2 (a warped image):
+ * the image as it is.  Otherwise with d = shifts + 3 k (the rounded drift, z x y) and bg = np.median(ims[k]):
+ * h[j] += ims[k][j + d] where j + d lies inside the stack and bg elsewhere, which is what `h += bg; h[dst] += im[src] - bg`
+ * leaves: every term and partial sum is a multiple of 0.5 far below 2^52, so the sum is exact in any order.  The medians
+ * are selected first, then the images are added in launches of up to 16, one read-modify-write of h per launch.
+ * backgrounds_out (optional, n): the medians used, 0 for a warped image.  IA3_EUNSUPPORTED for a stack that is not uint16,
+ * IA3_EINVAL for a shape other than h's and for |d| >= the axis length (NumPy cannot broadcast the two crops there). */
+int ia3_chrom_image_add_dev(ia3_chrom_image* h, const ia3_stack* const* ims, const int* flags, const int* shifts, int n,
+                            double* backgrounds_out);
+/* ia3_find_candidate_chromosomes_dev on a chromosome image, in the float64 arithmetic NumPy uses for a float64 ndarray:
+ * float64 plane medians (two middle values added and halved), IEEE float64 quotients, float64 seed.  Same outputs,
+ * limits and errors. */
+int ia3_find_candidate_chromosomes_f64_dev(const ia3_chrom_image* im, const ia3_chrom_params* p, double* coords_zxy,
+                                           int capacity, int* n_out, double* threshold, ia3_stack* kept_labels);
+
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
  * Per movie: raw (frames, X, Y) uint16 movie from host memory or a .dax file -> split_im_by_channels
