@@ -47,6 +47,7 @@ EXPORTS = [
     "ia3_label_centers_dev", "ia3_remove_small_labels_dev", "ia3_find_candidate_chromosomes_dev",
     "ia3_chrom_image_create", "ia3_chrom_image_free", "ia3_chrom_image_upload", "ia3_chrom_image_download",
     "ia3_chrom_image_add_dev", "ia3_stack_median_dev", "ia3_find_candidate_chromosomes_f64_dev",
+    "ia3_assign_nearest_dev", "ia3_select_chromosomes_dev",
 ]
 
 
@@ -721,6 +722,59 @@ def find_candidate_chromosomes(stack, filt_size, binary_per_th, morphology_size,
             kept.free()
         raise
     return coords[:n.value].copy(), np.float64(th.value), kept
+
+
+SELECT_THREADS, SELECT_TILE = 256, 256   # IA3_SELECT_THREADS, IA3_SELECT_TILE: spots of a workgroup, candidates of an LDS tile
+IA3_SELECT_EMPTY = 1                     # ia3_select_chromosomes_dev: every candidate was removed
+
+
+def _iptr(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int))
+
+
+def _scaled_table(zxy, what):
+    """(n, 3) C-contiguous float64 table of scaled coordinates, as ``cdist`` takes its arguments."""
+    t = np.ascontiguousarray(zxy, dtype=np.float64)
+    if t.ndim != 2 or t.shape[1] != 3:
+        raise ValueError("%s should be an (n, 3) table of scaled z, x, y, got shape %s" % (what, t.shape))
+    return t
+
+
+def assign_nearest(spots_zxy, cands_zxy):
+    """``ia3_assign_nearest_dev``: per row of ``spots_zxy`` the index of its nearest row of ``cands_zxy``
+    (``np.argmin(cdist(spots_zxy, cands_zxy), axis=1)``, int32)."""
+    s, c = _scaled_table(spots_zxy, "spots"), _scaled_table(cands_zxy, "candidates")
+    owner = np.empty(len(s), dtype=np.int32)
+    check(lib().ia3_assign_nearest_dev(dptr(s), len(s), dptr(c), len(c), _iptr(owner)))
+    return owner
+
+
+def select_chromosomes(spots_zxy, round_start, cands_zxy, loss_th, return_owner=False, times=False):
+    """``ia3_select_chromosomes_dev``: dict with ``removed`` (original indices in removal order), ``removed_lost`` (their
+    lost rounds when removed), ``lost`` (per candidate: the final count of a kept one, the count at its removal of a removed
+    one), ``visits``, ``empty`` (every candidate was removed), and on request ``owner`` (final owner per spot) and
+    ``times_ms`` (upload, first pass, removal loop)."""
+    s, c = _scaled_table(spots_zxy, "spots"), _scaled_table(cands_zxy, "candidates")
+    rs = np.ascontiguousarray(round_start, dtype=np.int32).ravel()
+    if len(rs) < 1 or rs[0] != 0 or rs[-1] != len(s) or (np.diff(rs) < 0).any():
+        raise ValueError("round_start should rise from 0 to the number of spots (%d)" % len(s))
+    removed, removed_lost = np.empty(len(c), dtype=np.int32), np.empty(len(c), dtype=np.int32)
+    lost = np.empty(len(c), dtype=np.int32)
+    owner = np.empty(len(s), dtype=np.int32) if return_owner else None
+    n, visits, t = C.c_int(0), C.c_longlong(0), np.zeros(3, dtype=np.float64)
+    rc = check(lib().ia3_select_chromosomes_dev(dptr(s), _iptr(rs), len(rs) - 1, dptr(c), len(c), C.c_double(float(loss_th)),
+                                                _iptr(removed), _iptr(removed_lost), C.byref(n), _iptr(lost),
+                                                None if owner is None else _iptr(owner), C.byref(visits),
+                                                dptr(t) if times else None), allow=(IA3_SELECT_EMPTY,))
+    removed, removed_lost = removed[:n.value].copy(), removed_lost[:n.value].copy()
+    lost[removed] = removed_lost
+    out = dict(removed=removed, removed_lost=removed_lost, lost=lost, visits=int(visits.value),
+               empty=rc == IA3_SELECT_EMPTY)
+    if return_owner:
+        out["owner"] = owner
+    if times:
+        out["times_ms"] = t
+    return out
 
 
 def poly_columns(order):

@@ -7,6 +7,9 @@ the chromosome image of an experiment without a chromosome stain: the float64 su
 ones moved by their drift.  The sum is kept on the device (``_lib.ChromImage``, csrc/chromim.hip) and
 ``segmentation_tools.chromosome.find_candidate_chromosomes`` takes it from there, bit for bit with the reference.
 
+``select_chromosome_by_candidate_spots`` is ``Field_of_View._select_chromosome_by_candidate_spots`` (:2273-2339): the
+candidates that keep a spot in enough rounds (csrc/select.hip).
+
 All ``file:line`` citations are relative to the reference tree.
 """
 import time
@@ -177,3 +180,32 @@ def generate_chrom_im_from_data(save_filename, data_type, num_loaded_image=10, f
         raise
     chrom.free()
     return out
+
+
+def select_chromosome_by_candidate_spots(spots_list, cand_chrom_coords, _good_chr_loss_th=0.4, _cand_spot_intensity_th=0.5,
+                                         _verbose=True, return_info=False):
+    """classes/field_of_view.py:2273-2339 ``Field_of_View._select_chromosome_by_candidate_spots`` on the spot tables of
+    every round (the ``{spot_type}_spots_list`` attribute) and the candidate centres (``cand_chrom_coords``): the
+    ``chrom_coords`` array of ``segmentation_tools.chromosome.select_candidate_chromosomes`` (:2325).  Loading the two from
+    the save file, keeping the result as an attribute and saving it are the caller's.
+
+    ``return_info=True``: ``(chrom_coords, removed, lost, chrom_spots)`` with the original indices of the removed candidates
+    in removal order, the rounds without a spot per candidate (at its removal for a removed one) and, per kept chromosome,
+    what ``spot_tools.picking.assign_spots_to_chromosomes`` gives it of every round's selected spots, taken from the owners
+    the device already holds.  ``lost`` and ``chrom_spots`` are None where the reference returns every candidate without
+    looking at a spot (``_good_chr_loss_th >= 1``, no rounds)."""
+    from ..segmentation_tools.chromosome import _select_chromosomes
+    from ..spot_tools.picking import split_rows_by_owner
+    _cand_chrom_coords = list(cand_chrom_coords)
+    _chrom_coords, info = _select_chromosomes(_cand_chrom_coords, spots_list, _cand_spot_intensity_th, _good_chr_loss_th,
+                                              _verbose, owners=return_info)
+    if not return_info:
+        return _chrom_coords
+    chrom_spots = None
+    if info["lost"] is not None:
+        chrom_spots = [[] for _ in _chrom_coords]
+        for sel, own in zip(info["sels"], info["owner"]):
+            per = split_rows_by_owner(sel, own, len(_chrom_coords)) if len(sel) else [[] for _ in _chrom_coords]
+            for i, rows in enumerate(per):
+                chrom_spots[i].append(rows)
+    return _chrom_coords, info["removed"], info["lost"], chrom_spots

@@ -133,10 +133,86 @@ def select_candidate_chromosomes(_cand_chrom_coords,
                                  _good_chr_loss_th=0.4,
                                  _verbose=True,
                                  ):
-    """segmentation_tools/chromosome.py:363-406 — not built (it depends on spot_tools.picking)."""
-    raise NotImplementedError("select_candidate_chromosomes is not built: it needs spot_tools.picking."
-                              "assign_spots_to_chromosomes; the candidates come from find_candidate_chromosomes, and "
-                              "segmentation_tools.morphology (label, remove_small_objects, label_centers) gives their labels")
+    """segmentation_tools/chromosome.py:363-406 — the candidates (z, x, y pixels) that lose a spot of intensity >=
+    ``_cand_spot_intensity_th`` in at most ``_good_chr_loss_th`` of the rounds of ``_spots_list``, after the worst
+    candidate has been removed one at a time and its spots handed to their next nearest candidate:
+    ``np.array(kept rows).copy()``, the reference's array, from one library call (``ia3_select_chromosomes_dev``,
+    DESIGN.md §21).  ``_good_chr_loss_th >= 1`` and an empty ``_spots_list`` return every candidate without the device;
+    no candidate at all, or the removal of the last one, raises ``NoChromosomeLeft`` (a ``ValueError``, as ``max()`` of the
+    reference's empty list)."""
+    _cand_chrom_coords = list(_cand_chrom_coords)
+    return _select_chromosomes(_cand_chrom_coords, _spots_list, _cand_spot_intensity_th, _good_chr_loss_th, _verbose)[0]
+
+
+# two bases: the reference's max([]) raises ValueError; callers from before this was built expect NotImplementedError
+class NoChromosomeLeft(ValueError, NotImplementedError):
+    pass
+
+
+_NONE_LEFT = ("max() arg is an empty sequence: no candidate chromosome is left for spot_tools.picking."
+              "assign_spots_to_chromosomes to assign spots to")
+
+
+def _cdist_table(zxy, name):
+    """What ``cdist`` makes of an argument, with its errors: a 2-D float64 table; three columns here."""
+    t = np.asarray(zxy, dtype=np.float64)
+    if t.ndim != 2:
+        raise ValueError("%s must be a 2-dimensional array." % name)
+    if t.shape[1] != 3:
+        raise ValueError("XA and XB must have the same number of columns (i.e. feature dimension.): z, x, y; %s has %d"
+                         % (name, t.shape[1]))
+    return t
+
+
+def _pack_rounds(_spots_list, _cand_spot_intensity_th, distance_zxy):
+    """:380-383 and picking.py:780-783 for every round: (selected rows per round, their scaled z, x, y of all rounds packed
+    into one float64 table, the R + 1 row offsets of the rounds)."""
+    sels, tables, starts = [], [], [0]
+    for _spots in _spots_list:
+        _spots = np.array(_spots)
+        _sel_spots = _spots[_spots[:, 0] >= _cand_spot_intensity_th]
+        sels.append(_sel_spots)
+        if len(_sel_spots):
+            tables.append(_cdist_table(_sel_spots[:, 1:4] * np.array(distance_zxy), "XA"))
+        starts.append(starts[-1] + len(_sel_spots))
+    zxys = np.concatenate(tables) if tables else np.zeros((0, 3), dtype=np.float64)
+    return sels, zxys, np.array(starts, dtype=np.int32)
+
+
+def _select_chromosomes(_cand_chrom_coords, _spots_list, _cand_spot_intensity_th, _good_chr_loss_th, _verbose,
+                        owners=False):
+    """The loop of :371-406 on the list ``_cand_chrom_coords``: (chrom_coords, info), info = dict of ``removed`` (original
+    indices in removal order), ``kept`` (original indices of the rows of chrom_coords), ``lost`` (rounds without a spot per
+    candidate, at its removal for a removed one; None when the loop never looked at a spot) and, with ``owners``, ``sels``
+    (the selected rows of every round) and ``owner`` (per round the row of chrom_coords that owns each selected row)."""
+    from .. import _distance_zxy
+    n_cand = len(_cand_chrom_coords)
+    if _verbose:
+        print(f"- start select from {n_cand} chromosomes with loss threshold={_good_chr_loss_th}")
+    if n_cand == 0:
+        raise NoChromosomeLeft(_NONE_LEFT)
+    info = dict(removed=np.zeros(0, dtype=np.int32), kept=np.arange(n_cand), lost=None)
+    n_rounds = len(_spots_list)
+    if 1 > _good_chr_loss_th and n_rounds > 0:      # :375-377: every flag starts at 1; np.mean of no rounds is NaN
+        _chrom_zxys = _cdist_table(np.array(_cand_chrom_coords) * np.array(_distance_zxy), "XB")
+        sels, zxys, starts = _pack_rounds(_spots_list, _cand_spot_intensity_th, _distance_zxy)
+        res = L.select_chromosomes(zxys, starts, _chrom_zxys, _good_chr_loss_th, return_owner=owners)
+        alive = np.ones(n_cand, dtype=bool)
+        for c, lost in zip(res["removed"], res["removed_lost"]):
+            if _verbose:
+                print(f"-- remove chr id {int(alive[:c].sum())}, percentage of lost rounds:{np.float64(lost) / n_rounds:.3f}.")
+            alive[c] = False
+        if res["empty"]:
+            raise NoChromosomeLeft(_NONE_LEFT)
+        info = dict(removed=res["removed"], kept=np.flatnonzero(alive), lost=res["lost"])
+        if owners:
+            row = np.cumsum(alive) - 1             # original index -> row of chrom_coords
+            info["sels"] = sels
+            info["owner"] = [row[res["owner"][a:b]] for a, b in zip(starts[:-1], starts[1:])]
+    _chrom_coords = np.array([_cand_chrom_coords[i] for i in info["kept"]]).copy()
+    if _verbose:
+        print(f"-- {len(_chrom_coords)} chromosomes are kept.")
+    return _chrom_coords, info
 
 
 def identify_chromosomes(chrom_im, dapi_im=None,

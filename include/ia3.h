@@ -698,6 +698,32 @@ int ia3_chrom_image_add_dev(ia3_chrom_image* h, const ia3_stack* const* ims, con
 int ia3_find_candidate_chromosomes_f64_dev(const ia3_chrom_image* im, const ia3_chrom_params* p, double* coords_zxy,
                                            int capacity, int* n_out, double* threshold, ia3_stack* kept_labels);
 
+/* ---- chromosome selection by candidate spots (select.hip) ------------------------------------------------
+ * spot_tools/picking.py:767-794 assign_spots_to_chromosomes and the loop of segmentation_tools/chromosome.py:377-399
+ * select_candidate_chromosomes.  Both take coordinates that are already scaled by distance_zxy (host NumPy), as n x 3 and
+ * n_cand x 3 float64 host tables, n_cand >= 1 (at most 2^22).  The distance is scipy's cdist,
+ * sqrt((dz*dz + dx*dx) + dy*dy) with every operation rounded to float64 on its own, and the owner of a spot is np.argmin of
+ * its row: the first NaN if there is one, otherwise the first candidate whose ROOT is the smallest.
+ * ia3_assign_nearest_dev: owner[i] (n ints) = that candidate for spot i. */
+#define IA3_SELECT_THREADS 256   /* spots of one workgroup */
+#define IA3_SELECT_TILE 256      /* candidates staged in LDS at a time */
+#define IA3_SELECT_EMPTY 1       /* ia3_select_chromosomes_dev: every candidate was removed (outputs are complete) */
+int ia3_assign_nearest_dev(const double* spots_zxy, int n, const double* cands_zxy, int n_cand, int* owner);
+/* The selected spots of all n_rounds rounds packed in round order, round r = rows round_start[r] .. round_start[r + 1]
+ * (round_start[0] = 0; an empty round repeats its start).  lost[c] = the rounds in which candidate c owns no spot; while the
+ * largest double(lost) / n_rounds over the alive candidates is > loss_th, that candidate (the lowest index among equals) is
+ * removed and only the spots it owned get a new owner among the alive ones.  removed[k] / removed_lost[k] (n_cand ints
+ * each): index and lost of the k-th removed candidate, *n_removed their number; lost (n_cand ints): the final values (of a
+ * removed candidate: undefined); owner (optional, n ints): the final owner of every spot; visits (optional): candidates
+ * visited = n * n_cand + sum over the removals of (spots the candidate owned) * (candidates alive after it); times_ms
+ * (optional, 3 doubles): host clock of the upload, the first pass and the removal loop, each ended by a synchronise
+ * (the final downloads of lost and owner are in none of the three).
+ * n_rounds = 0 removes nothing.  Returns IA3_SELECT_EMPTY when the last candidate was removed.  The host reads one
+ * 8-byte record per removal step (four steps are queued per look); nothing that scales with n or n_cand moves between the first upload and the last download. */
+int ia3_select_chromosomes_dev(const double* spots_zxy, const int* round_start, int n_rounds, const double* cands_zxy,
+                               int n_cand, double loss_th, int* removed, int* removed_lost, int* n_removed, int* lost,
+                               int* owner, long long* visits, double* times_ms);
+
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
  * Per movie: raw (frames, X, Y) uint16 movie from host memory or a .dax file -> split_im_by_channels
