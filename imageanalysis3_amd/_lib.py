@@ -19,7 +19,7 @@ OFFSET_ALIGNMENT_TOOLS, OFFSET_FITTING_V4 = 0, 1    # fftalign_2d offset convent
 
 EXPORTS = [
     "ia3_init", "ia3_last_error", "ia3_version", "ia3_device_name", "ia3_sync", "ia3_stream",
-    "ia3_release_workspace", "ia3_workspace_stats", "ia3_seed_skip_stats", "ia3_prepare_depth", "ia3_col_guard", "ia3_col_weights", "ia3_profile_enable", "ia3_profile_collect", "ia3_set_tuning",
+    "ia3_release_workspace", "ia3_workspace_stats", "ia3_seed_skip_stats", "ia3_seed_bg_stats", "ia3_prepare_depth", "ia3_col_guard", "ia3_col_weights", "ia3_profile_enable", "ia3_profile_collect", "ia3_set_tuning",
     "ia3_stack_upload", "ia3_stack_alloc", "ia3_stack_load_file", "ia3_stack_wrap", "ia3_stack_download", "ia3_stack_info",
     "ia3_stack_free",
     "ia3_gaussian_filter", "ia3_gaussian_filter_dev", "ia3_gaussian_highpass", "ia3_gaussian_highpass_dev",

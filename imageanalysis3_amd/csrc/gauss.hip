@@ -921,6 +921,7 @@ int ia3_set_tuning(int key, int value) {
   if (key == IA3_TUNE_SEED_STRIPS) { ia3k::set_seed_strips(value); return 0; }
   if (key == IA3_TUNE_SEED_FUSED) { ia3k::set_seed_fused(value); return 0; }
   if (key == IA3_TUNE_SEED_SKIP) { ia3k::set_seed_skip(value); return 0; }
+  if (key == IA3_TUNE_SEED_BGORDER) { ia3k::set_seed_bgorder(value); return 0; }
   if (key == IA3_TUNE_FIT_NBLIST) { ia3k::set_fit_nblist(value); return 0; }
   if (key == IA3_TUNE_FFT_C2C) { ia3k::set_fft_c2c(value); return 0; }
   if (key == IA3_TUNE_FIT_FUSE) { ia3k::set_fit_fuse(value); return 0; }

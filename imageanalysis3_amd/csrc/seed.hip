@@ -18,6 +18,7 @@
 #include "ia3_rt.h"
 #include "ia3_gauss_dev.h"
 #include "ia3_seedskip.h"
+#include "ia3_bgtest.h"
 #include <memory>
 #include <algorithm>
 #include <math.h>
@@ -741,153 +742,197 @@ template <> __device__ __forceinline__ float quant<uint16_t>(double v) { return 
 
 struct TapsD { double w[64]; };   // w[j] = tap at offset j (symmetric), j <= R
 
-// One 576-thread block per candidate (grid-stride), one wave per row: exact min_im at the candidate and its 26
-// neighbours from the axis-0 result zp.
-//   rows r = 3 * dz + dx (z' = clamp(z + dz - 1), x' = clamp(x + dx - 1)), positions i = 0 .. 2R+2 <-> y'' = y - 1 - R + i
-//   (reflected): trow[r][i] = axis-1 pass of zp at (z', x', y''), quantised to the stack dtype (lanes run along i, so
-//   every load is a contiguous row piece; the nine rows go side by side because the pass is a chain of dependent
-//   loads); then lane k < 27 of wave 0 runs the axis-2 pass at (row k / 3, y' = clamp(y + k % 3 - 1)) over its row in
-//   LDS.  Both passes: acc = in[0] * w0; for j = R..1: acc = acc + (in[-j] + in[+j]) * w[j]  (this file is compiled
-//   with -ffp-contract=off), as NI_Correlate1D and the dense kernels do.
+// (double)v through a register the compiler cannot look into: bg_sparse3_k's three chains convert each of their 63 loaded
+// values where they use it instead of keeping 63 doubles (126 registers) alive next to them.  Same value, same bits.
+__device__ __forceinline__ double fresh_f64(float v) { asm volatile("" : "+v"(v)); return (double)v; }
+__device__ __forceinline__ double fresh_f64(uint16_t v) { unsigned u = v; asm volatile("" : "+v"(u)); return (double)u; }
+
+// The sparse background pass: exact min_im at a first-stage candidate and its neighbours from the axis-0 result zp, then
+// the reference's two tests in the order of ia3_bgtest.h: the centre plane z first (nine values), the planes z - 1 and
+// z + 1 only for a candidate whose answer needs them (early = 0: for every candidate).  mval[9 dz + 3 dx + dy] is min_im at
+// (clamp(z + dz - 1), clamp(x + dx - 1), clamp(y + dy - 1)).
+//   one plane z' = clamp(z + dz - 1): rows dx (x' = clamp(x + dx - 1)), positions i = 0 .. 2R+2 <-> y'' = y - 1 - R + i
+//   (reflected): trow[dx][i] = axis-1 pass of zp at (z', x', y''), quantised to the stack dtype (lanes run along i, so
+//   every load is a contiguous row piece); then nine lanes run the axis-2 pass at (row dx, y' = clamp(y + dy - 1)) over
+//   their row in LDS.  Both passes: acc = in[0] * w0; for j = R..1: acc = acc + (in[-j] + in[+j]) * w[j]  (this file is
+//   compiled with -ffp-contract=off), as NI_Correlate1D and the dense kernels do.
+// A plane that clamps onto plane z (z = 0 or Z - 1) holds the centre plane's values: they are copied, not gathered again.
+// ctl->pad[0] counts the candidates that took the outer planes (ia3_seed_bg_stats).
+
+// Any radius: one 192-thread block per candidate (grid-stride), one wave per row of the plane in hand; the decision is
+// block-uniform (every thread reads the same mval).
 template <class T>
-__global__ __launch_bounds__(576) void bg_sparse_k(const T* __restrict__ zp, int Z, int X, int Y, TapsD taps, int R, int mode,
+__global__ __launch_bounds__(192) void bg_sparse_k(const T* __restrict__ zp, int Z, int X, int Y, TapsD taps, int R, int mode,
                                                    const Cand0* __restrict__ c0, const SeedCtl* __restrict__ ctl0,
                                                    unsigned cap0, double th_low, Cand* __restrict__ out, unsigned capacity,
-                                                   SeedCtl* __restrict__ ctl) {
+                                                   SeedCtl* __restrict__ ctl, int early) {
   constexpr int NI = 2 * 63 + 3;              // positions per row at the largest supported radius
-  __shared__ float trow[9][NI + 1];
+  __shared__ float trow[3][NI + 1];
   __shared__ float mval[32];
-  const int r = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int dx = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const unsigned n0 = ctl0->n_cand < cap0 ? ctl0->n_cand : cap0;
   const int ni = 2 * R + 3;
+  unsigned n_outer = 0;
   for (unsigned c = blockIdx.x; c < n0; c += gridDim.x) {   // block-uniform
     const Cand0 k = c0[c];
-    {   // ---- axis 1 on row r ----
-      const int zz = min(max(k.z + r / 3 - 1, 0), Z - 1), xx = min(max(k.x + r % 3 - 1, 0), X - 1);
-      const T* pl = zp + (size_t)zz * X * Y;
-      for (int i = lane; i < ni; i += 64) {
-        const int yy = reflect_idx(k.y - 1 - R + i, Y, mode);
-        double acc = (double)pl[(size_t)xx * Y + yy] * taps.w[0];
+    int verdict = ia3bg::BG_OUTER;
+    float diff = 0.f;
+#pragma unroll 1
+    for (int step = 0; step < 3; ++step) {   // planes z, z - 1, z + 1
+      const int dz = step == 0 ? 1 : (step == 1 ? 0 : 2);
+      const int zz = min(max(k.z + dz - 1, 0), Z - 1);
+      if (step > 0 && zz == k.z) {   // (block-uniform) clamped onto the centre plane
+        if (threadIdx.x < 9) mval[9 * dz + threadIdx.x] = mval[9 + threadIdx.x];
+      } else {
+        {   // ---- axis 1 on row dx ----
+          const int xx = min(max(k.x + dx - 1, 0), X - 1);
+          const T* pl = zp + (size_t)zz * X * Y;
+          for (int i = lane; i < ni; i += 64) {
+            const int yy = reflect_idx(k.y - 1 - R + i, Y, mode);
+            double acc = (double)pl[(size_t)xx * Y + yy] * taps.w[0];
 #pragma unroll 8
-        for (int j = R; j >= 1; --j) {
-          const double a = (double)pl[(size_t)reflect_idx(xx - j, X, mode) * Y + yy];
-          const double b = (double)pl[(size_t)reflect_idx(xx + j, X, mode) * Y + yy];
-          acc = acc + (a + b) * taps.w[j];
+            for (int j = R; j >= 1; --j) {
+              const double a = (double)pl[(size_t)reflect_idx(xx - j, X, mode) * Y + yy];
+              const double b = (double)pl[(size_t)reflect_idx(xx + j, X, mode) * Y + yy];
+              acc = acc + (a + b) * taps.w[j];
+            }
+            trow[dx][i] = quant<T>(acc);
+          }
         }
-        trow[r][i] = quant<T>(acc);
+        __syncthreads();
+        // ---- axis 2 at the nine positions of the plane ----
+        if (threadIdx.x < 9) {
+          const int rr = threadIdx.x / 3;
+          const int yc = min(max(k.y + (int)threadIdx.x % 3 - 1, 0), Y - 1);
+          const int i0 = yc - (k.y - 1 - R);        // in [R, R + 2]
+          const float* t = trow[rr];
+          // reflect(yc + j) = reflect(y - 1 - R + (i0 + j)): the row array already holds the reflected positions
+          double acc = (double)t[i0] * taps.w[0];
+          for (int j = R; j >= 1; --j) acc = acc + ((double)t[i0 - j] + (double)t[i0 + j]) * taps.w[j];
+          mval[9 * dz + threadIdx.x] = quant<T>(acc);
+        }
+      }
+      __syncthreads();   // mval of this plane complete; trow free for the next one
+      if (step == 0 && early) {
+        verdict = ia3bg::centre_step(mval + 9, k.cmax, th_low, &diff);
+        if (verdict != ia3bg::BG_OUTER) break;   // block-uniform
       }
     }
-    __syncthreads();
-    // ---- axis 2 at the 27 neighbourhood positions ----
-    if (threadIdx.x < 27) {
-      const int rr = threadIdx.x / 3;
-      const int yc = min(max(k.y + (int)threadIdx.x % 3 - 1, 0), Y - 1);
-      const int i0 = yc - (k.y - 1 - R);        // in [R, R + 2]
-      const float* t = trow[rr];
-      // reflect(yc + j) = reflect(y - 1 - R + (i0 + j)): the row array already holds the reflected positions
-      double acc = (double)t[i0] * taps.w[0];
-      for (int j = R; j >= 1; --j) acc = acc + ((double)t[i0 - j] + (double)t[i0 + j]) * taps.w[j];
-      mval[threadIdx.x] = quant<T>(acc);
+    if (verdict == ia3bg::BG_OUTER) {
+      ++n_outer;
+      verdict = ia3bg::full_step(mval, k.cmax, th_low, &diff) ? ia3bg::BG_ACCEPT : ia3bg::BG_REJECT;
     }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float cmin = mval[13];
-      float vmin = cmin;
-      for (int q = 0; q < 27; ++q) vmin = mval[q] < vmin ? mval[q] : vmin;
-      const float diff = k.cmax - cmin;                       // float32(max_im) - float32(min_im), fitting.py:106
-      if (vmin != cmin && (double)diff >= th_low) {
-        const unsigned pos = atomicAdd(&ctl->n_cand, 1u);
-        if (pos < capacity) out[pos] = Cand{k.z, k.x, k.y, diff};
-        else ctl->overflow = 1;
-      }
+    if (threadIdx.x == 0 && verdict == ia3bg::BG_ACCEPT) {
+      const unsigned pos = atomicAdd(&ctl->n_cand, 1u);
+      if (pos < capacity) out[pos] = Cand{k.z, k.x, k.y, diff};
+      else ctl->overflow = 1;
     }
-    __syncthreads();   // the next candidate's rows overwrite trow
+    __syncthreads();   // the next candidate's planes overwrite mval
   }
+  if (threadIdx.x == 0 && n_outer) atomicAdd(&ctl->pad[0], n_outer);
 }
 
-// The same computation for the production radius (RC = 30 at compile time) with one WAVE per plane z' and three waves per
-// candidate.  The three rows x' = x - 1, x, x + 1 of a plane take their 61 axis-1 taps from 63 consecutive rows of the
-// stack: a lane loads those 63 values once (all in flight together, row starts in scalar registers) and runs the three
-// chains on registers, instead of 3 x 61 loads in eight dependent batches.  Candidates whose 63 rows touch the border
-// of the stack (reflection, clamped x') take the row-by-row code of bg_sparse_k.  Same operations in the same order.
+// The same computation for the production radius (RC = 30 at compile time) with one WAVE per candidate: four candidates
+// to a 256-thread block, no block barrier.  The three rows x' = x - 1, x, x + 1 of a plane take their 61 axis-1 taps from
+// 63 consecutive rows of the stack: a lane loads those 63 values once (all in flight together, row starts in scalar
+// registers) and runs the three chains on registers, instead of 3 x 61 loads in eight dependent batches.  Candidates whose
+// 63 rows touch the border of the stack (reflection, clamped x') take the row-by-row code of bg_sparse_k.  Same operations
+// in the same order.  trow and mval are private to the wave: its LDS writes and reads are ordered by wave barriers.
 template <class T, int RC>
-__global__ __launch_bounds__(192) void bg_sparse3_k(const T* __restrict__ zp, int Z, int X, int Y, TapsD taps, int mode,
+__global__ __launch_bounds__(256) void bg_sparse3_k(const T* __restrict__ zp, int Z, int X, int Y, TapsD taps, int mode,
                                                     const Cand0* __restrict__ c0, const SeedCtl* __restrict__ ctl0,
                                                     unsigned cap0, double th_low, Cand* __restrict__ out, unsigned capacity,
-                                                    SeedCtl* __restrict__ ctl) {
+                                                    SeedCtl* __restrict__ ctl, int early) {
   constexpr int NI = 2 * RC + 3;              // positions per row; also the rows a lane loads
   static_assert(NI <= 64, "one lane per position");
-  __shared__ float trow[9][NI + 1];
-  __shared__ float mval[32];
-  const int dzw = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  __shared__ float trow_s[4][3][64];
+  __shared__ float mval_s[4][32];
+  const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6)), lane = threadIdx.x & 63;
+  float (*trow)[64] = trow_s[wv];
+  float* mval = mval_s[wv];
   const unsigned n0 = ctl0->n_cand < cap0 ? ctl0->n_cand : cap0;
-  for (unsigned c = blockIdx.x; c < n0; c += gridDim.x) {   // block-uniform
+  unsigned n_outer = 0;
+  for (unsigned c = blockIdx.x * 4u + (unsigned)wv; c < n0; c += gridDim.x * 4u) {   // wave-uniform
     const Cand0 k = c0[c];
     const int kz = __builtin_amdgcn_readfirstlane(k.z), kx = __builtin_amdgcn_readfirstlane(k.x),
               ky = __builtin_amdgcn_readfirstlane(k.y);
-    const int zz = min(max(kz + dzw - 1, 0), Z - 1);
-    const T* pl = zp + (size_t)zz * X * Y;
-    if (kx - 1 - RC >= 0 && kx + 1 + RC < X) {   // block-uniform
-      if (lane < NI) {
-        const unsigned yy = (unsigned)reflect_idx(ky - 1 - RC + lane, Y, mode);
-        const T* base = pl + (size_t)(kx - 1 - RC) * Y;
-        T v[NI];
+    int verdict = ia3bg::BG_OUTER;
+    float diff = 0.f;
+#pragma unroll 1
+    for (int step = 0; step < 3; ++step) {   // planes z, z - 1, z + 1
+      const int dz = step == 0 ? 1 : (step == 1 ? 0 : 2);
+      const int zz = min(max(kz + dz - 1, 0), Z - 1);
+      if (step > 0 && zz == kz) {   // (wave-uniform) clamped onto the centre plane
+        if (lane < 9) mval[9 * dz + lane] = mval[9 + lane];
+      } else {
+        const T* pl = zp + (size_t)zz * X * Y;
+        if (kx - 1 - RC >= 0 && kx + 1 + RC < X) {   // wave-uniform
+          if (lane < NI) {
+            const unsigned yy = (unsigned)reflect_idx(ky - 1 - RC + lane, Y, mode);
+            const T* base = pl + (size_t)(kx - 1 - RC) * Y;
+            T v[NI];
 #pragma unroll
-        for (int m = 0; m < NI; ++m) v[m] = (base + (size_t)m * Y)[yy];
+            for (int m = 0; m < NI; ++m) v[m] = (base + (size_t)m * Y)[yy];
 #pragma unroll
-        for (int dx = 0; dx < 3; ++dx) {
-          double acc = (double)v[RC + dx] * taps.w[0];
+            for (int dx = 0; dx < 3; ++dx) {
+              double acc = fresh_f64(v[RC + dx]) * taps.w[0];
 #pragma unroll
-          for (int j = RC; j >= 1; --j) acc = acc + ((double)v[RC + dx - j] + (double)v[RC + dx + j]) * taps.w[j];
-          trow[3 * dzw + dx][lane] = quant<T>(acc);
-        }
-      }
-    } else {
-      for (int dx = 0; dx < 3; ++dx) {
-        const int xx = min(max(kx + dx - 1, 0), X - 1);
-        if (lane < NI) {
-          const int yy = reflect_idx(ky - 1 - RC + lane, Y, mode);
-          double acc = (double)pl[(size_t)xx * Y + yy] * taps.w[0];
-#pragma unroll 8
-          for (int j = RC; j >= 1; --j) {
-            const double a = (double)pl[(size_t)reflect_idx(xx - j, X, mode) * Y + yy];
-            const double b = (double)pl[(size_t)reflect_idx(xx + j, X, mode) * Y + yy];
-            acc = acc + (a + b) * taps.w[j];
+              for (int j = RC; j >= 1; --j) acc = acc + (fresh_f64(v[RC + dx - j]) + fresh_f64(v[RC + dx + j])) * taps.w[j];
+              trow[dx][lane] = quant<T>(acc);
+            }
           }
-          trow[3 * dzw + dx][lane] = quant<T>(acc);
+        } else {
+          for (int dx = 0; dx < 3; ++dx) {
+            const int xx = min(max(kx + dx - 1, 0), X - 1);
+            if (lane < NI) {
+              const int yy = reflect_idx(ky - 1 - RC + lane, Y, mode);
+              double acc = (double)pl[(size_t)xx * Y + yy] * taps.w[0];
+#pragma unroll 8
+              for (int j = RC; j >= 1; --j) {
+                const double a = (double)pl[(size_t)reflect_idx(xx - j, X, mode) * Y + yy];
+                const double b = (double)pl[(size_t)reflect_idx(xx + j, X, mode) * Y + yy];
+                acc = acc + (a + b) * taps.w[j];
+              }
+              trow[dx][lane] = quant<T>(acc);
+            }
+          }
+        }
+        __builtin_amdgcn_wave_barrier();
+        // ---- axis 2 at the nine positions of the plane ----
+        if (lane < 9) {
+          const int rr = lane / 3;
+          const int yc = min(max(ky + lane % 3 - 1, 0), Y - 1);
+          const int i0 = yc - (ky - 1 - RC);        // in [RC, RC + 2]
+          const float* t = trow[rr];
+          float ta[RC], tb[RC];
+#pragma unroll
+          for (int j = 1; j <= RC; ++j) { ta[j - 1] = t[i0 - j]; tb[j - 1] = t[i0 + j]; }
+          double acc = (double)t[i0] * taps.w[0];
+#pragma unroll
+          for (int j = RC; j >= 1; --j) acc = acc + ((double)ta[j - 1] + (double)tb[j - 1]) * taps.w[j];
+          mval[9 * dz + lane] = quant<T>(acc);
         }
       }
-    }
-    __syncthreads();
-    // ---- axis 2 at the 27 neighbourhood positions ----
-    if (threadIdx.x < 27) {
-      const int rr = threadIdx.x / 3;
-      const int yc = min(max(ky + (int)threadIdx.x % 3 - 1, 0), Y - 1);
-      const int i0 = yc - (ky - 1 - RC);        // in [RC, RC + 2]
-      const float* t = trow[rr];
-      float ta[RC], tb[RC];
-#pragma unroll
-      for (int j = 1; j <= RC; ++j) { ta[j - 1] = t[i0 - j]; tb[j - 1] = t[i0 + j]; }
-      double acc = (double)t[i0] * taps.w[0];
-#pragma unroll
-      for (int j = RC; j >= 1; --j) acc = acc + ((double)ta[j - 1] + (double)tb[j - 1]) * taps.w[j];
-      mval[threadIdx.x] = quant<T>(acc);
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-      const float cmin = mval[13];
-      float vmin = cmin;
-      for (int q = 0; q < 27; ++q) vmin = mval[q] < vmin ? mval[q] : vmin;
-      const float diff = k.cmax - cmin;                       // float32(max_im) - float32(min_im), fitting.py:106
-      if (vmin != cmin && (double)diff >= th_low) {
-        const unsigned pos = atomicAdd(&ctl->n_cand, 1u);
-        if (pos < capacity) out[pos] = Cand{k.z, k.x, k.y, diff};
-        else ctl->overflow = 1;
+      __builtin_amdgcn_wave_barrier();   // mval of this plane complete; trow free for the next one
+      if (step == 0 && early) {
+        verdict = __builtin_amdgcn_readfirstlane(ia3bg::centre_step(mval + 9, k.cmax, th_low, &diff));
+        if (verdict != ia3bg::BG_OUTER) break;   // wave-uniform
       }
     }
-    __syncthreads();   // the next candidate's rows overwrite trow
+    if (verdict == ia3bg::BG_OUTER) {
+      ++n_outer;
+      verdict = __builtin_amdgcn_readfirstlane(ia3bg::full_step(mval, k.cmax, th_low, &diff) ? ia3bg::BG_ACCEPT : ia3bg::BG_REJECT);
+    }
+    if (lane == 0 && verdict == ia3bg::BG_ACCEPT) {
+      const unsigned pos = atomicAdd(&ctl->n_cand, 1u);
+      if (pos < capacity) out[pos] = Cand{kz, kx, ky, diff};
+      else ctl->overflow = 1;
+    }
+    __builtin_amdgcn_wave_barrier();   // the next candidate's planes overwrite mval
   }
+  if (lane == 0 && n_outer) atomicAdd(&ctl->pad[0], n_outer);
 }
+
 
 template <class T>
 void launch_detect(int W, const void* mx, const void* mn, int Z, int X, int Y, int edge, double th_low,
@@ -930,7 +975,7 @@ namespace {
 constexpr unsigned FIN_CAP = 32768;    // candidates the first kernel looks at
 constexpr unsigned FIN_KEYS = 16384;   // ... of which at most this many may pass the chosen level
 constexpr int FIN_S = 8;               // slices of the all-pairs loops (grid.y)
-struct FinCtl { unsigned n_alive; int chosen; unsigned n_cand, overflow; unsigned done, n_kept, pad[2]; };   // n_cand / overflow mirror SeedCtl
+struct FinCtl { unsigned n_alive; int chosen; unsigned n_cand, overflow; unsigned done, n_kept, pad[2]; unsigned bg_tested, bg_outer; };   // n_cand / overflow mirror SeedCtl
 
 __device__ __forceinline__ unsigned fin_n(const SeedCtl* sctl) { return sctl->n_cand < FIN_CAP ? sctl->n_cand : FIN_CAP; }
 __device__ __forceinline__ unsigned long long fin_key(const Cand& k) {   // h desc, then z, x, y desc (finish_seeds)
@@ -1061,9 +1106,11 @@ __global__ __launch_bounds__(256) void fin_scatter_k(const SeedCtl* __restrict__
   fcw->n_cand = nc;
   fcw->overflow = ov;
   fcw->pad[0] = lazy ? lazy->pad[0] : 0u;   // planes seed_front_k ran
+  fcw->bg_tested = lazy ? (lazy->n_cand < cap0 ? lazy->n_cand : cap0) : 0u;   // candidates of the sparse background pass
+  fcw->bg_outer = lazy ? sctl->pad[0] : 0u;                                    // ... that took the outer planes
   if (mail) {   // the four control words straight into the host's pinned mailbox, then the sequence number it polls
     mail[1] = fcw->n_alive; mail[2] = (unsigned)fcw->chosen; mail[3] = nc; mail[4] = ov;
-    mail[5] = fcw->pad[0];
+    mail[5] = fcw->pad[0]; mail[6] = fcw->bg_tested; mail[7] = fcw->bg_outer;
     __threadfence_system();
     mail[0] = seq;
   }
@@ -1145,6 +1192,12 @@ int g_seed_skip = 2;
 void set_seed_skip(int v) { g_seed_skip = v < 0 ? 0 : (v > 2 ? 2 : v); }
 // (tile, plane) units of the calling thread's last seed stage: run by seed_front_k / in all (ia3_seed_skip_stats)
 static thread_local double t_skip_run = 0, t_skip_all = 0;
+// IA3_TUNE_SEED_BGORDER: 1 (default) = the sparse background pass tests the centre plane first and gathers the planes
+// z - 1 and z + 1 only for the candidates whose answer needs them (ia3_bgtest.h); 0 = all three planes for every candidate
+int g_seed_bgorder = 1;
+void set_seed_bgorder(int on) { g_seed_bgorder = on ? 1 : 0; }
+// candidates of the calling thread's last seed stage: tested by the sparse pass / that took the outer planes (ia3_seed_bg_stats)
+static thread_local double t_bg_tested = 0, t_bg_outer = 0;
 
 constexpr unsigned LAZY_CAP = 1u << 17;   // first-stage candidates of the lazy background path (2 MB)
 
@@ -1195,12 +1248,17 @@ static void launch_lazy(const void* mx, const void* zp, int Z, int X, int Y, con
     ProfScope ps("seed_sparse_bg");
     TapsD t;
     for (int j = 0; j < 64; ++j) t.w[j] = j <= R ? w[R + j] : 0.0;
-    if (R == 30)   // the production radius: 0.163 -> 0.128 ms for 5 000 candidates (grids of 1024 / 2048 / 8192 blocks: 0.158 / 0.134 / 0.129)
-      hipLaunchKernelGGL((bg_sparse3_k<T, 30>), dim3(4096), dim3(192), 0, s, (const T*)zp, Z, X, Y, t, IA3_MODE_REFLECT,
-                         (const Cand0*)c0, (const SeedCtl*)ctl0, LAZY_CAP, th_low, out, capacity, ctl);
+    // the production radius: one wave per candidate, four to a block.  5 000 float32 candidates, centre plane first: grids
+    // of 768 / 1024 / 1280 / 2048 blocks: 0.085 / 0.086 / 0.084 / 0.084 ms (all three planes for every candidate: 0.170 /
+    // 0.185 / 0.182 / 0.182 ms); the three-waves-per-candidate kernel before it: 0.127 ms.  1280 blocks = one wave per
+    // candidate up to 5 120 of them.  (With 63 doubles kept beside the chains, three waves per SIMD instead of four:
+    // 512 / 1024 / 2048 / 4096 blocks: 0.102 / 0.092 / 0.095 / 0.095 ms.)
+    if (R == 30)
+      hipLaunchKernelGGL((bg_sparse3_k<T, 30>), dim3(1280), dim3(256), 0, s, (const T*)zp, Z, X, Y, t, IA3_MODE_REFLECT,
+                         (const Cand0*)c0, (const SeedCtl*)ctl0, LAZY_CAP, th_low, out, capacity, ctl, g_seed_bgorder);
     else
-    hipLaunchKernelGGL((bg_sparse_k<T>), dim3(4096), dim3(576), 0, s, (const T*)zp, Z, X, Y, t, R, IA3_MODE_REFLECT,
-                       (const Cand0*)c0, (const SeedCtl*)ctl0, LAZY_CAP, th_low, out, capacity, ctl);
+      hipLaunchKernelGGL((bg_sparse_k<T>), dim3(4096), dim3(192), 0, s, (const T*)zp, Z, X, Y, t, R, IA3_MODE_REFLECT,
+                         (const Cand0*)c0, (const SeedCtl*)ctl0, LAZY_CAP, th_low, out, capacity, ctl, g_seed_bgorder);
   }
 }
 
@@ -1236,6 +1294,7 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
                          bool low_list = false) {
   hipStream_t s = stream();
   t_skip_run = t_skip_all = 0;
+  t_bg_tested = t_bg_outer = 0;
   const bool dbg = getenv("IA3_DEBUG_TIMING") != nullptr;
   const double t0 = now_ms();
   const int Z = im->Z, X = im->X, Y = im->Y;
@@ -1472,6 +1531,7 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
         }
         hfc.n_alive = mb[1]; hfc.chosen = (int)mb[2]; hfc.n_cand = mb[3]; hfc.overflow = mb[4];
         if (fused) t_skip_run = (double)mb[5];
+        hfc.bg_tested = mb[6]; hfc.bg_outer = mb[7];
         dbg_stamp("seed count seen");
       } else {
         if (fe == hipSuccess) fe = hipMemcpyAsync(&hfc, fc, sizeof(FinCtl), hipMemcpyDeviceToHost, s);
@@ -1479,6 +1539,7 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
         if (fe == hipSuccess && fused) t_skip_run = (double)hfc.pad[0];
       }
       if (fe != hipSuccess) return set_error(IA3_EHIP, "seed finish failed: %s", hipGetErrorString(fe));
+      t_bg_tested = (double)hfc.bg_tested; t_bg_outer = (double)hfc.bg_outer;
       if (hfc.overflow & 2u)     // more first-stage candidates than the lazy path is sized for: dense filter instead
         return dog_seed_impl(im, p, out, dev, true);
       if (top_list && hfc.chosen != 0)   // level 0 has too few seeds: the list at th[0] does not hold the other levels' seeds
@@ -1506,6 +1567,7 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
     memcpy(&hctl, hbuf.data(), sizeof(SeedCtl));
     memcpy(&hlazy, hbuf.data() + sizeof(SeedCtl), sizeof(SeedCtl));
     if (fused) t_skip_run = (double)hlazy.pad[0];
+    if (lazy) { t_bg_tested = (double)(hlazy.n_cand < LAZY_CAP ? hlazy.n_cand : LAZY_CAP); t_bg_outer = (double)hctl.pad[0]; }
     if (lazy && (hlazy.overflow || hlazy.n_cand > LAZY_CAP)) return dog_seed_impl(im, p, out, dev, true);
     if (hctl.n_cand <= capacity) {
       cand.resize(hctl.n_cand);
@@ -1736,6 +1798,12 @@ int ia3_seed_in_distance(const void* im, int dtype, int Z, int X, int Y, const d
 int ia3_seed_skip_stats(double* out2) {
   if (!out2) return set_error(IA3_EINVAL, "null output");
   out2[0] = ia3k::t_skip_run; out2[1] = ia3k::t_skip_all;
+  return IA3_OK;
+}
+
+int ia3_seed_bg_stats(double* out2) {
+  if (!out2) return set_error(IA3_EINVAL, "null output");
+  out2[0] = ia3k::t_bg_tested; out2[1] = ia3k::t_bg_outer;
   return IA3_OK;
 }
 

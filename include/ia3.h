@@ -70,6 +70,10 @@ int ia3_workspace_stats(double* out6);
 /* the fused seed detector's (tile, plane) units of the calling thread's last get_seeds: out2 = {units filtered and tested,
    units in all}; {0, 0} when that call did not run the fused detector (see IA3_TUNE_SEED_SKIP) */
 int ia3_seed_skip_stats(double* out2);
+/* the sparse background pass of the calling thread's last get_seeds: out2 = {first-stage candidates it tested, those of
+   them for which it evaluated the planes z - 1 and z + 1}; {0, 0} when that call ran the dense filter (see
+   IA3_TUNE_SEED_BGORDER) */
+int ia3_seed_bg_stats(double* out2);
 /* per-kernel timing with HIP events on the library stream (off by default) */
 int ia3_profile_enable(int on);
 int ia3_profile_collect(char* buf, int len); /* "kernel,count,total_ms\n" lines since last collect */
@@ -150,6 +154,12 @@ int ia3_profile_collect(char* buf, int len); /* "kernel,count,total_ms\n" lines 
  * pass unless its kernels are already loaded: no call starts the compiler.  fit_spots_by_segmentation, which filters one
  * crop per cell, each of a depth of its own, sets it around its loop.  Results are identical bit for bit. */
 #define IA3_TUNE_COL_RTC 17
+/* IA3_TUNE_SEED_BGORDER: 1 (default) = the sparse background pass of the lazy seed detector evaluates min_im on the
+ * candidate's own plane first (nine values) and decides from them where it can: rejected below the threshold, accepted
+ * with an in-plane neighbour below the centre; only the other candidates get the planes z - 1 and z + 1 (csrc/ia3_bgtest.h
+ * states why this is the reference's test for every input); 0 = the same kernels evaluate all 27 values for every
+ * candidate.  Seeds are identical bit for bit. */
+#define IA3_TUNE_SEED_BGORDER 18
 /* IA3_DEBUG_FIT_MAXFEV: PROFILING ONLY, changes results: > 0 caps the function evaluations of every fit (MINPACK's maxfev),
  * which splits the fit kernel's time into its fixed and its per-evaluation part; 0 (default) = the reference's limits. */
 #define IA3_DEBUG_FIT_MAXFEV 100
