@@ -48,6 +48,9 @@ EXPORTS = [
     "ia3_chrom_image_create", "ia3_chrom_image_free", "ia3_chrom_image_upload", "ia3_chrom_image_download",
     "ia3_chrom_image_add_dev", "ia3_stack_median_dev", "ia3_find_candidate_chromosomes_f64_dev",
     "ia3_assign_nearest_dev", "ia3_select_chromosomes_dev",
+    "ia3_pick_create", "ia3_pick_free", "ia3_pick_by_intensity_dev", "ia3_pick_set_rows", "ia3_pick_reference_dev",
+    "ia3_pick_set_sorted", "ia3_pick_scores_dev", "ia3_pick_difference_dev", "ia3_pick_download", "ia3_pick_download_sorted",
+    "ia3_pick_cum_vals_dev",
 ]
 
 
@@ -147,6 +150,7 @@ def lib():
         L.ia3_fit_destroy.restype = None
         L.ia3_drift_ref_free.restype = None
         L.ia3_chrom_image_free.restype = None
+        L.ia3_pick_free.restype = None
         _lib = L
     return _lib
 
@@ -775,6 +779,213 @@ def select_chromosomes(spots_zxy, round_start, cands_zxy, loss_th, return_owner=
     if times:
         out["times_ms"] = t
     return out
+
+
+PICK_MAX_CHANNELS = 8                    # IA3_PICK_MAX_CHANNELS
+PICK_KEYS = PICK_MAX_CHANNELS + 1        # keys per kind in the flat [kind][key] tables of ia3_pick_*
+PICK_KINDS = ("ct", "lc", "int")         # kind 0, 1, 2: centre distance, local-centre distance, intensity
+PICK_ROWS_PICKS, PICK_ROWS_PREV, PICK_ROWS_REF = 0, 1, 2
+(PICK_GET_PICKS, PICK_GET_PREV, PICK_GET_SEL_SCORES, PICK_GET_PICK_INDEX, PICK_GET_SCORES, PICK_GET_MIDS,
+ PICK_GET_CAND_DISTS, PICK_GET_REF_CT, PICK_GET_REF_LOCAL, PICK_GET_REF_INT) = range(10)
+PICK_NITER_MAX = 15                      # cum_val's niter_max (picking.py:1879)
+
+
+def cum_vals(sorted_vals, targets):
+    """``ia3_pick_cum_vals_dev``: per target the last ``mid`` of the reference's ``cum_val`` search (int32)."""
+    v = np.ascontiguousarray(sorted_vals, dtype=np.float64).ravel()
+    t = np.ascontiguousarray(targets, dtype=np.float64).ravel()
+    if len(v) == 0:
+        raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+    mids = np.empty(len(t), dtype=np.int32)
+    check(lib().ia3_pick_cum_vals_dev(dptr(v), len(v), dptr(t), len(t), _iptr(mids)))
+    return mids
+
+
+def pick_search_nodes(n):
+    """``mid`` of every node that a ``cum_val`` search in ``n`` sorted values can visit, indexed by heap number (root 1, a
+    true compare goes to 2 * node + 1; -1: not reachable).  At most 2^16 entries whatever ``n`` is: the search stops after
+    16 iterations.  One level of (m, M) pairs per pass."""
+    n = int(n)
+    if n < 1:
+        raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+    node, m, M = np.array([1], dtype=np.int64), np.array([0], dtype=np.int64), np.array([n - 1], dtype=np.int64)
+    found = []
+    for it in range(PICK_NITER_MAX + 1):
+        mid = (m + M) >> 1
+        found.append((node, mid))
+        if it == PICK_NITER_MAX:
+            break
+        node = np.concatenate([2 * node + 1, 2 * node])
+        m, M = np.concatenate([mid, m]), np.concatenate([M, mid])
+        live = M - m >= 2
+        node, m, M = node[live], m[live], M[live]
+        if len(node) == 0:
+            break
+    size = 2
+    while size <= int(found[-1][0].max()):
+        size *= 2
+    mids = np.full(size, -1, dtype=np.int64)
+    for node, mid in found:
+        mids[node] = mid
+    return mids
+
+
+def pick_log_tables(n):
+    """(``np.log(mid / n)``, ``np.log(1 - mid / n)``) per heap number of ``pick_search_nodes(n)``, with ``mid = 0.5`` where the
+    node's mid is 0 (picking.py:1895-1899) and NaN for a number that no search reaches: this host's ``np.log``."""
+    mids = pick_search_nodes(n)
+    v = mids.astype(np.float64)
+    v[mids == 0] = 0.5
+    v = v / float(n)
+    v[mids < 0] = np.nan
+    with np.errstate(invalid="ignore"):
+        return np.log(v), np.log(1 - v)
+
+
+class PickPopulation(object):
+    """A population of P chromosomes x R regions with its candidate spots resident in HBM (owner of an
+    ``ia3_pick_population`` handle), and on it the steps of the reference's population picker (picking.py:1567-2342).
+    Keys of the reference arrays are channel numbers ``0..n_channels-1`` and ``n_channels`` for 'all'."""
+
+    def __init__(self, handle, P, R, n, n_channels):
+        self._h = handle
+        self.P, self.R, self.n, self.n_channels = P, R, n, n_channels
+        self.lengths = np.full((3, PICK_KEYS), -1, dtype=np.int32)   # of the resident sorted reference arrays
+        self._logs = {}                                             # (kind, key) -> (length, log table)
+
+    @classmethod
+    def upload(cls, cands, region_start, row_1d, P, R, channel=None, n_channels=0):
+        """``cands``: (n, 4) float64 (h, z, x, y in nm) packed in (chromosome, region) order; ``region_start``: P*R + 1
+        offsets; ``row_1d``: P*R flags, 1 where the entry was ONE 1-D row; ``channel``: R small ints or None."""
+        t = np.ascontiguousarray(cands, dtype=np.float64).reshape(-1, 4)
+        rs = np.ascontiguousarray(region_start, dtype=np.int32).ravel()
+        fl = np.ascontiguousarray(row_1d, dtype=np.uint8).ravel()
+        P, R = int(P), int(R)
+        if len(rs) != P * R + 1 or len(fl) != P * R:
+            raise ValueError("PickPopulation.upload: %d offsets and %d flags for %d x %d regions" % (len(rs), len(fl), P, R))
+        ch = None
+        if channel is not None:
+            ch = np.ascontiguousarray(channel, dtype=np.int32).ravel()
+            if len(ch) != R:
+                raise ValueError("PickPopulation.upload: %d channels for %d regions" % (len(ch), R))
+        h = C.c_void_p()
+        check(lib().ia3_pick_create(dptr(t), len(t), _iptr(rs), fl.ctypes.data_as(C.POINTER(C.c_ubyte)), P, R,
+                                    None if ch is None else _iptr(ch), int(n_channels) if ch is not None else 0, C.byref(h)))
+        return cls(h, P, R, len(t), int(n_channels) if ch is not None else 0)
+
+    def _rows(self, rows):
+        t = np.ascontiguousarray(rows, dtype=np.float64)
+        if t.size != self.P * self.R * 4:
+            raise ValueError("a (%d, %d, 4) table is required, got shape %s" % (self.P, self.R, t.shape))
+        return t
+
+    def set_rows(self, which, rows):
+        check(lib().ia3_pick_set_rows(self._h, int(which), dptr(self._rows(rows))))
+
+    def pick_by_intensity(self):
+        check(lib().ia3_pick_by_intensity_dev(self._h))
+
+    @staticmethod
+    def _window(win_start, win_idx, R):
+        ws = np.ascontiguousarray(win_start, dtype=np.int32).ravel()
+        wi = np.ascontiguousarray(win_idx, dtype=np.int32).ravel()
+        if len(ws) != R + 1 or ws[-1] != len(wi):
+            raise ValueError("a window table of %d + 1 offsets is required" % R)
+        return ws, wi
+
+    def _centers(self, centers):
+        if centers is None:
+            return None
+        c = np.ascontiguousarray(centers, dtype=np.float64)
+        if c.shape != (self.P, 3):
+            raise ValueError("centres should be (%d, 3), got %s" % (self.P, c.shape))
+        return c
+
+    def reference(self, win_start, win_idx, split=False, centers=None, ref_is_picks=True):
+        """E-step on the resident picks; returns the (3, PICK_KEYS) lengths of the sorted reference arrays (-1: not made)."""
+        ws, wi = self._window(win_start, win_idx, self.R)
+        c = self._centers(centers)
+        lengths = np.full((3, PICK_KEYS), -1, dtype=np.int32)
+        check(lib().ia3_pick_reference_dev(self._h, _iptr(ws), _iptr(wi), 1 if split else 0, None if c is None else dptr(c),
+                                           1 if ref_is_picks else 0, _iptr(lengths)))
+        self.lengths = lengths
+        return lengths
+
+    def set_sorted(self, kind, key, values):
+        v = np.ascontiguousarray(values, dtype=np.float64).ravel()
+        check(lib().ia3_pick_set_sorted(self._h, int(kind), int(key), dptr(v), len(v)))
+        self.lengths[kind, key] = len(v)
+
+    def scores(self, win_start, win_idx, split_int=False, split_dist=False, center_weight=1.0, local_weight=1.0, centers=None,
+               ref_is_picks=True, dist_only=False):
+        """M-step with the resident reference arrays.  The log tables of the arrays a score reads are made here from their
+        lengths (kept while a length stays the same).  IndexError when such an array is empty, as in the reference."""
+        ws, wi = self._window(win_start, win_idx, self.R)
+        c = self._centers(centers)
+        tabs, sizes, keep = (C.c_void_p * (3 * PICK_KEYS))(), np.zeros(3 * PICK_KEYS, dtype=np.int32), []
+        if not dist_only:
+            for kind in range(3):
+                if (kind == 0 and center_weight == 0) or (kind == 1 and local_weight == 0):
+                    continue
+                split = split_int if kind == 2 else split_dist
+                for key in (range(self.n_channels) if split else (self.n_channels,)):
+                    n = int(self.lengths[kind, key])
+                    if n < 1:
+                        raise IndexError("index 0 is out of bounds for axis 0 with size 0")
+                    if self._logs.get((kind, key), (None,))[0] != n:
+                        lo, lo1 = pick_log_tables(n)
+                        self._logs[(kind, key)] = (n, np.ascontiguousarray(lo if kind == 2 else lo1))
+                    t = self._logs[(kind, key)][1]
+                    keep.append(t)
+                    tabs[kind * PICK_KEYS + key] = t.ctypes.data
+                    sizes[kind * PICK_KEYS + key] = len(t)
+        check(lib().ia3_pick_scores_dev(self._h, _iptr(ws), _iptr(wi), 1 if split_int else 0, 1 if split_dist else 0,
+                                        C.c_double(float(center_weight)), C.c_double(float(local_weight)),
+                                        None if c is None else dptr(c), 1 if ref_is_picks else 0, tabs, _iptr(sizes),
+                                        1 if dist_only else 0))
+
+    def difference(self):
+        """(rows whose pick moved by less than 0.01, rows whose distance is not NaN) between the previous and the current
+        picks: the 8-byte record of ``ia3_pick_difference_dev``."""
+        out = np.zeros(2, dtype=np.int32)
+        check(lib().ia3_pick_difference_dev(self._h, _iptr(out)))
+        return int(out[0]), int(out[1])
+
+    def download(self, what):
+        PR, n = self.P * self.R, self.n
+        shape, dt = {PICK_GET_PICKS: ((self.P, self.R, 4), np.float64), PICK_GET_PREV: ((self.P, self.R, 4), np.float64),
+                     PICK_GET_SEL_SCORES: ((self.P, self.R), np.float64), PICK_GET_PICK_INDEX: ((self.P, self.R), np.int32),
+                     PICK_GET_SCORES: ((n,), np.float64), PICK_GET_MIDS: ((n, 3), np.int32),
+                     PICK_GET_CAND_DISTS: ((n, 2), np.float64), PICK_GET_REF_CT: ((self.P, self.R), np.float64),
+                     PICK_GET_REF_LOCAL: ((self.P, self.R), np.float64), PICK_GET_REF_INT: ((self.P, self.R), np.float64)}[what]
+        out = np.empty(shape, dtype=dt)
+        check(lib().ia3_pick_download(self._h, int(what), ptr(out)))
+        return out
+
+    def sorted_reference(self, kind, key):
+        n = int(self.lengths[kind, key])
+        if n < 0:
+            raise KeyError((kind, key))
+        out = np.empty(n, dtype=np.float64)
+        check(lib().ia3_pick_download_sorted(self._h, int(kind), int(key), dptr(out)))
+        return out
+
+    def free(self):
+        if self._h is not None:
+            lib().ia3_pick_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
 
 
 def poly_columns(order):

@@ -734,6 +734,61 @@ int ia3_select_chromosomes_dev(const double* spots_zxy, const int* round_start, 
                                int n_cand, double loss_th, int* removed, int* removed_lost, int* n_removed, int* lost,
                                int* owner, long long* visits, double* times_ms);
 
+/* ---- population spot picking (pick.hip) -------------------------------------------------------------------
+ * spot_tools/picking.py:1567-2342: pick_spots_by_intensities, generate_reference_from_population (E-step),
+ * pick_spots_by_scores (M-step), evaluate_differences and cum_val, on a population of P chromosomes x R regions that is
+ * uploaded once and stays resident over the EM iterations.  Candidates: one packed n x 4 float64 table (h, z, x, y in nm);
+ * region_start[P*R + 1]: CSR over (chromosome, region); row_1d[P*R]: 1 where the entry was given as ONE 1-D row (its norms
+ * are BLAS ddot's sqrt(fma(dy,dy,fma(dx,dx,dz*dz))), those of a 2-D table sqrt((dz*dz+dx*dx)+dy*dy)); channel[R] in
+ * 0..n_channels-1 (NULL and 0: no channels).  A key is a channel, or n_channels for 'all'; a kind is 0 centre distance,
+ * 1 local-centre distance, 2 intensity.  Tables indexed [kind][key] are flat with IA3_PICK_MAX_CHANNELS + 1 keys per kind.
+ * The local window of region j (:1689-1699) comes from the caller as CSR over reference indices in summation order:
+ * win_idx[win_start[j] .. win_start[j + 1]), each in 0..R-1; np.nanmean adds the rows in that order.
+ * Nothing that scales with P*R or n moves between create and the downloads: a step uploads the window table (R-sized),
+ * optional centres (P x 3) and log tables (at most 2^16 values each), and reads back lengths or the 8-byte difference. */
+#define IA3_PICK_MAX_CHANNELS 8
+enum { IA3_PICK_ROWS_PICKS = 0, IA3_PICK_ROWS_PREV = 1, IA3_PICK_ROWS_REF = 2 };
+enum { IA3_PICK_GET_PICKS = 0, IA3_PICK_GET_PREV = 1, IA3_PICK_GET_SEL_SCORES = 2, IA3_PICK_GET_PICK_INDEX = 3,
+       IA3_PICK_GET_SCORES = 4, IA3_PICK_GET_MIDS = 5, IA3_PICK_GET_CAND_DISTS = 6, IA3_PICK_GET_REF_CT = 7,
+       IA3_PICK_GET_REF_LOCAL = 8, IA3_PICK_GET_REF_INT = 9 };
+typedef struct ia3_pick_population ia3_pick_population;
+int ia3_pick_create(const double* cands, int n, const int* region_start, const unsigned char* row_1d, int P, int R,
+                    const int* channel, int n_channels, ia3_pick_population** out);
+void ia3_pick_free(ia3_pick_population* h);
+/* :1723-1749: picks[p][r] = the first row of maximal h (np.argmax: the first NaN wins), a NaN row for an empty region */
+int ia3_pick_by_intensity_dev(ia3_pick_population* h);
+/* uploads a P*R x 4 table as the picks, the previous picks or the reference rows (IA3_PICK_ROWS_*) */
+int ia3_pick_set_rows(ia3_pick_population* h, int which, const double* rows);
+/* E-step (:1751-1876) of the picks against the reference rows (the picks themselves when ref_is_picks): per (chromosome,
+ * region) the centre distance (centre: centers_zxy[P x 3], or NULL for the nanmean of the picks, per channel when split),
+ * the local-centre distance and the intensity; their non-NaN values become the sorted reference arrays of 'all' and, when
+ * split, of every channel.  lengths[kind][key]: the arrays' lengths, -1 for one that was not made. */
+int ia3_pick_reference_dev(ia3_pick_population* h, const int* win_start, const int* win_idx, int split,
+                           const double* centers_zxy, int ref_is_picks, int* lengths);
+/* a sorted reference array given by the caller instead */
+int ia3_pick_set_sorted(ia3_pick_population* h, int kind, int key, const double* values, int n);
+/* M-step (:1906-2013): per candidate the distances, the three cum_val mids (order: centre, local, intensity; -1 for a
+ * term whose weight is 0) and the score log_int + center_weight * log_ct + local_weight * log_lc (separate float64
+ * operations, a term skipped when its weight is 0); per region the selected row (np.argmax: the first NaN, else the first
+ * maximum), its score (np.nanmax) and its index in the region (-1: empty).  The picks become the previous picks and the
+ * selection the picks.  logtabs[kind][key] (host, logsizes values): for every array a score reads, indexed by the heap
+ * number of the search node a cum_val ends on (root 1, a true compare goes to 2 * node + 1), np.log(mid / n) for kind 2
+ * and np.log(1 - mid / n) for kinds 0 and 1, mid = 0.5 where the node's mid is 0, evaluated by the host's NumPy.
+ * A table is a function of its array's length alone: it is copied to the device only when that length (or logsizes) differs
+ * from the one the resident table was made for.
+ * IA3_EINVAL when an array a score reads is empty (the reference's IndexError).  dist_only: the distances alone. */
+int ia3_pick_scores_dev(ia3_pick_population* h, const int* win_start, const int* win_idx, int split_int, int split_dist,
+                        double center_weight, double local_weight, const double* centers_zxy, int ref_is_picks,
+                        const double* const* logtabs, const int* logsizes, int dist_only);
+/* :2280-2284: counts[0] = rows whose picks moved by less than 0.01, counts[1] = rows whose distance is not NaN */
+int ia3_pick_difference_dev(ia3_pick_population* h, int* counts);
+/* IA3_PICK_GET_*: picks / previous picks (P*R x 4 float64), selected scores (P*R float64), pick index (P*R int32), scores
+ * (n float64), mids (n x 3 int32), candidate distances (n x 2 float64: centre, local), the E-step's values (P*R float64) */
+int ia3_pick_download(ia3_pick_population* h, int what, void* out);
+int ia3_pick_download_sorted(ia3_pick_population* h, int kind, int key, double* out);
+/* :1879-1899 cum_val alone: mids[i] = the last mid of the search for targets[i] in sorted_vals[0..n), n >= 1 */
+int ia3_pick_cum_vals_dev(const double* sorted_vals, int n, const double* targets, int m, int* mids);
+
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
  * Per movie: raw (frames, X, Y) uint16 movie from host memory or a .dax file -> split_im_by_channels
