@@ -51,6 +51,7 @@ EXPORTS = [
     "ia3_pick_create", "ia3_pick_free", "ia3_pick_by_intensity_dev", "ia3_pick_set_rows", "ia3_pick_reference_dev",
     "ia3_pick_set_sorted", "ia3_pick_scores_dev", "ia3_pick_difference_dev", "ia3_pick_download", "ia3_pick_download_sorted",
     "ia3_pick_cum_vals_dev",
+    "ia3_dist_create", "ia3_dist_free", "ia3_dist_summary_dev", "ia3_dist_contact_stack_dev",
 ]
 
 
@@ -128,6 +129,16 @@ class MovieJob(C.Structure):
                 ("stamps", C.c_double * 6)]
 
 
+_DP, _IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
+# argument types of the ia3_dist_* entries as include/ia3.h declares them (an opaque handle is a void pointer)
+DIST_PROTOTYPES = {
+    "ia3_dist_create": (C.c_int, [_DP, _IP, C.c_int, C.POINTER(C.c_void_p)]),
+    "ia3_dist_free": (None, [C.c_void_p]),
+    "ia3_dist_summary_dev": (C.c_int, [C.c_void_p, _IP, _IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _DP, _IP,
+                                       _IP]),
+    "ia3_dist_contact_stack_dev": (C.c_int, [_DP, C.c_longlong, C.c_longlong, C.c_double, _DP, _IP, _IP]),
+}
+
 _lib = None
 
 
@@ -151,6 +162,9 @@ def lib():
         L.ia3_drift_ref_free.restype = None
         L.ia3_chrom_image_free.restype = None
         L.ia3_pick_free.restype = None
+        for name, (res, args) in DIST_PROTOTYPES.items():
+            fn = getattr(L, name)
+            fn.restype, fn.argtypes = res, args
         _lib = L
     return _lib
 
@@ -409,6 +423,7 @@ def crop_pairs(stack_a, centers_a, crop, stack_b=None, centers_b=None, regress=F
 
 CUBE_MAX_RADIUS = 10          # largest search radius of the cube lookups (csrc/ia3_labels.h)
 IA3_TUNE_COL_RTC = 17
+IA3_TUNE_DIST_TILE = 19
 
 
 def _centres(centers_zxy):
@@ -1206,3 +1221,89 @@ def process_movies(params, movies, drifts_in=None, measure_drift=True, want_imag
                         ms=dict(upload=j.t_upload_ms, correct=j.t_correct_ms, fit=j.t_fit_ms),
                         stamps=[float(v) for v in j.stamps]))
     return out
+
+
+DIST_NANMEDIAN, DIST_NANMEAN, DIST_CONTACT = 0, 1, 2      # IA3_DIST_*
+
+
+class DistancePopulation(object):
+    """The (rows, 3) float64 coordinate tables of M chromosome copies resident in HBM (owner of an
+    ``ia3_dist_population`` handle), and on it the summaries of structure_tools/distance.py over pairs of copies."""
+
+    def __init__(self, handle, rows):
+        self._h = handle
+        self.rows = rows                  # rows of every copy (int32)
+        self.M = len(rows)
+
+    @classmethod
+    def upload(cls, tables):
+        """``tables``: a sequence of M (rows, 3) arrays, one per chromosome copy (z, x, y)."""
+        ts = []
+        for t in tables:
+            a = np.ascontiguousarray(t, dtype=np.float64)
+            if a.ndim != 2 or a.shape[1] != 3:
+                raise ValueError("DistancePopulation.upload: a (rows, 3) table is required, got shape %s" % (a.shape,))
+            ts.append(a)
+        if len(ts) < 1:
+            raise ValueError("DistancePopulation.upload: no tables")
+        rows = np.array([len(a) for a in ts], dtype=np.int32)
+        start = np.zeros(len(ts) + 1, dtype=np.int32)
+        np.cumsum(rows, out=start[1:])
+        packed = np.ascontiguousarray(np.concatenate(ts, axis=0)) if start[-1] > 0 else np.zeros((1, 3))
+        h = C.c_void_p()
+        check(lib().ia3_dist_create(dptr(packed), _iptr(start), len(ts), C.byref(h)))
+        return cls(h, rows)
+
+    def summary(self, pair_a, pair_b, function=DIST_NANMEDIAN, contact_th=None, same=False, return_counts=False):
+        """``ia3_dist_summary_dev`` over the pairs (pair_a[n], pair_b[n]): the (Ra, Rb) float64 summary, with
+        ``return_counts`` also (n_finite, n_contact) as int32.  ValueError for no pair, an index outside the population and
+        pairs whose tables differ in rows."""
+        a = np.ascontiguousarray(pair_a, dtype=np.int32).ravel()
+        b = np.ascontiguousarray(pair_b, dtype=np.int32).ravel()
+        if len(a) != len(b) or len(a) < 1:
+            raise ValueError("DistancePopulation.summary: %d and %d copy indices (at least one pair is required)" % (len(a), len(b)))
+        if a.min() < 0 or b.min() < 0 or a.max() >= self.M or b.max() >= self.M:
+            raise ValueError("DistancePopulation.summary: a copy index outside 0..%d" % (self.M - 1))
+        Ra, Rb = int(self.rows[a[0]]), int(self.rows[b[0]])
+        if (self.rows[a] != Ra).any() or (self.rows[b] != Rb).any():
+            raise ValueError("DistancePopulation.summary: the tables of the pairs do not all have %d and %d rows" % (Ra, Rb))
+        if Ra < 1 or Rb < 1:
+            raise ValueError("DistancePopulation.summary: a %d x %d summary" % (Ra, Rb))
+        out = np.empty((Ra, Rb), dtype=np.float64)
+        nf = np.empty((Ra, Rb), dtype=np.int32) if return_counts else None
+        nc = np.empty((Ra, Rb), dtype=np.int32) if return_counts else None
+        th = float("nan") if contact_th is None else float(contact_th)
+        check(lib().ia3_dist_summary_dev(self._h, _iptr(a), _iptr(b), len(a), Ra, Rb, 1 if same else 0, int(function),
+                                         C.c_double(th), dptr(out), None if nf is None else _iptr(nf),
+                                         None if nc is None else _iptr(nc)))
+        return (out, nf, nc) if return_counts else out
+
+    def free(self):
+        if self._h is not None:
+            lib().ia3_dist_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+def dist_contact_stack(stack, contact_th, return_counts=False):
+    """``ia3_dist_contact_stack_dev``: ``contact_prob`` along axis 0 of an (N, ...) float64 stack."""
+    v = np.ascontiguousarray(stack, dtype=np.float64)
+    if v.ndim < 1 or v.shape[0] < 1 or v.size < 1:
+        raise ValueError("dist_contact_stack: a stack of at least one value is required, got shape %s" % (v.shape,))
+    N, K = v.shape[0], v.size // v.shape[0]
+    prob = np.empty(v.shape[1:], dtype=np.float64)
+    nf, nc = np.empty(v.shape[1:], dtype=np.int32), np.empty(v.shape[1:], dtype=np.int32)
+    check(lib().ia3_dist_contact_stack_dev(dptr(v), C.c_longlong(N), C.c_longlong(K), C.c_double(float(contact_th)), dptr(prob),
+                                           _iptr(nf), _iptr(nc)))
+    return (prob, nf, nc) if return_counts else prob

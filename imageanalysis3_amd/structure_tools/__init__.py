@@ -1,0 +1,4 @@
+"""structure_tools — what a tracing experiment is run for: the median distance map and the contact-probability map of a
+population of picked chromosomes (distance.py: Chr2ZxysList_2_summaryDist_by_key, Chr2ZxysList_2_summaryDict, contact_prob
+and the plotting-order helpers), summarised on the device without the stack of per-cell matrices.  contact.py,
+chromosome.py and what builds on the maps (domain_tools, compartment_tools, the figures) stay the reference's."""

@@ -160,6 +160,10 @@ int ia3_profile_collect(char* buf, int len); /* "kernel,count,total_ms\n" lines 
  * states why this is the reference's test for every input); 0 = the same kernels evaluate all 27 values for every
  * candidate.  Seeds are identical bit for bit. */
 #define IA3_TUNE_SEED_BGORDER 18
+/* IA3_TUNE_DIST_TILE: output tile of the median kernel of ia3_dist_summary_dev.  0 (default) = 2 x 2 entries per workgroup
+ * (64 lanes per entry) while 4 x 4 tiles would be fewer than two per compute unit, 4 x 4 (sixteen lanes per entry)
+ * otherwise; 2, 4 or 8 = that tile for every shape (8 x 8: four lanes per entry).  Results are identical bit for bit. */
+#define IA3_TUNE_DIST_TILE 19
 /* IA3_DEBUG_FIT_MAXFEV: PROFILING ONLY, changes results: > 0 caps the function evaluations of every fit (MINPACK's maxfev),
  * which splits the fit kernel's time into its fixed and its per-evaluation part; 0 (default) = the reference's limits. */
 #define IA3_DEBUG_FIT_MAXFEV 100
@@ -788,6 +792,36 @@ int ia3_pick_download(ia3_pick_population* h, int what, void* out);
 int ia3_pick_download_sorted(ia3_pick_population* h, int kind, int key, double* out);
 /* :1879-1899 cum_val alone: mids[i] = the last mid of the search for targets[i] in sorted_vals[0..n), n >= 1 */
 int ia3_pick_cum_vals_dev(const double* sorted_vals, int n, const double* targets, int m, int* mids);
+
+/* ---- summaries of population distance maps (distsum.hip) ----------------------------------------------------
+ * structure_tools/distance.py:12-67: per chromosome pair the stack of squareform(pdist(zxys)) / cdist(zxys1, zxys2)
+ * matrices over all cells and homolog combinations, reduced along the stack by np.nanmedian, np.nanmean or contact_prob.
+ * The stack is never made.  A population is the packed rows x 3 float64 (z, x, y) tables of M chromosome copies, copy m =
+ * rows copy_start[m] .. copy_start[m + 1]; it is uploaded once (region-major per group of copies with equally many rows)
+ * and stays resident.  A summary names N >= 1 pairs of copies whose tables have Ra and Rb rows.  The distance is scipy's,
+ * sqrt(q) with q = (dz*dz + dx*dx) + dy*dy, every operation rounded to float64 on its own; same = 1: pair_a[n] ==
+ * pair_b[n] and the diagonal is squareform's literal 0, also for a row of NaNs.
+ *   IA3_DIST_NANMEDIAN  per entry the middle one of the sorted values that are not NaN, (lo + hi) / 2.0 of the two middle
+ *                       ones for an even count, NaN for none: selected on q (sqrt is monotone), two roots per entry
+ *   IA3_DIST_NANMEAN    the roots added in the order of n with NaN as 0 (pairwise, as NumPy, when Ra * Rb == 1), over the
+ *                       count of values that are not NaN
+ *   IA3_DIST_CONTACT    n_contact / n_finite in float64 (0 / 0: NaN), n_contact = values <= contact_th counted as
+ *                       q <= q* (csrc/ia3_distsum.h: the largest double whose root is <= contact_th; no contact for a
+ *                       negative or NaN threshold, every value that is not NaN for +inf), n_finite = finite values
+ * out: Ra x Rb float64; n_finite / n_contact: optional Ra x Rb int32 (contact_th is read only for them and for
+ * IA3_DIST_CONTACT).  Host pointers.  Device memory of a call beyond the resident tables: 2 N ints and 16 Ra Rb bytes,
+ * whatever N * Ra * Rb is; nothing of that size is made, moved or downloaded.  IA3_EINVAL: N < 1, a copy index outside
+ * 0..M-1, a pair whose tables do not have Ra / Rb rows, same with pair_a[n] != pair_b[n]. */
+enum { IA3_DIST_NANMEDIAN = 0, IA3_DIST_NANMEAN = 1, IA3_DIST_CONTACT = 2 };
+typedef struct ia3_dist_population ia3_dist_population;
+int ia3_dist_create(const double* zxys, const int* copy_start, int M, ia3_dist_population** out);
+void ia3_dist_free(ia3_dist_population* h);
+int ia3_dist_summary_dev(ia3_dist_population* h, const int* pair_a, const int* pair_b, int N, int Ra, int Rb, int same,
+                         int function, double contact_th, double* out, int* n_finite, int* n_contact);
+/* distance.py:231-232 contact_prob of an (N, K) float64 stack the caller holds (host): `value <= contact_th` on the values
+ * themselves over np.isfinite; prob: K float64, n_finite / n_contact: optional K int32 */
+int ia3_dist_contact_stack_dev(const double* stack, long long N, long long K, double contact_th, double* prob, int* n_finite,
+                               int* n_contact);
 
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
