@@ -1105,7 +1105,7 @@ def make_seed_params(th_seed, gfilt_size=0.75, background_gfilt_size=7.5, filt_s
     p.dynamic_niters = int(dynamic_niters)
     p.min_dynamic_seeds = int(min_dynamic_seeds)
     p.remove_hot_pixel = 1 if remove_hot_pixel else 0
-    p.hot_pixel_th = int(hot_pixel_th)
+    p.hot_pixel_th = int(np.ceil(hot_pixel_th))   # counts >= th (fitting.py:136) on integers
     p.max_num_seeds = int(max_num_seeds) if (max_num_seeds is not None and max_num_seeds > 0) else 0
     if p.gfilt_size > 0:
         w, r = gaussian_taps(p.gfilt_size)

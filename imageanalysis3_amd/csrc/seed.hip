@@ -1493,7 +1493,9 @@ static int dog_seed_impl(const ia3_stack* im, const ia3_seed_params& p, SeedOut&
       char* fb = (char*)fin;
       hipError_t fe;
       FinCtl* fc = (FinCtl*)fb;
-      const int hot_th = p.remove_hot_pixel ? p.hot_pixel_th : 0;
+      // the kernels read hot_th <= 0 as "rule off".  With the rule on, a threshold <= 0 makes every column hot
+      // (fitting.py:136: counts >= hot_pixel_th) and no seed survives, as in finish_seeds: a candidate counts itself, so 1 does that
+      const int hot_th = p.remove_hot_pixel ? (p.hot_pixel_th > 1 ? p.hot_pixel_th : 1) : 0;
       void *mail_host = nullptr, *mail_dev = nullptr;
       static thread_local unsigned t_seq = 0;
       const unsigned seq = ++t_seq ? t_seq : ++t_seq;   // never 0 (the mailbox starts zeroed)
@@ -1846,6 +1848,8 @@ int ia3_dog_filters_dev(const ia3_stack* im, double sigma_front, double sigma_ba
 int ia3_dog_seed(const void* im, int dtype, int Z, int X, int Y, const ia3_seed_params* p,
                  double* out_zxyh, int capacity, int* n_out, double* th_used) {
   ia3_stack* a = nullptr;
+  if (p && (p->filt_size < 1 || p->filt_size > 8))   // as dog_seed_impl, before the stack goes to the device
+    return set_error(IA3_EUNSUPPORTED, "filt_size %d not in 1..8", p->filt_size);
   int rc = ia3_stack_upload(im, dtype, Z, X, Y, &a); if (rc) return rc;
   rc = ia3_dog_seed_dev(a, p, out_zxyh, capacity, n_out, th_used);
   ia3_stack_free(a);

@@ -17,7 +17,8 @@ known-answer tests only.
 Third-party arithmetic the reference delegates to and this oracle keeps delegating to:
 ``scipy.optimize.leastsq`` (MINPACK lmder), ``scipy.spatial.cKDTree`` / ``Delaunay``,
 ``scipy.signal.fftconvolve``.  ``scipy.ndimage`` filters are restated in NumPy with the exact
-summation order of ``NI_Correlate1D`` so the HIP kernels have a line-by-line model.
+summation order of ``NI_Correlate1D`` so the HIP kernels have a line-by-line model (rank filters of a size
+other than 3 go through ``scipy.ndimage`` itself: a maximum or minimum has no rounding to restate).
 
 All ``file:line`` citations are relative to /root/reference/.
 """
@@ -96,6 +97,16 @@ def minimum_filter3(a):
     return _rank3(a, np.minimum)
 
 
+def _rank_filter(a, size, is_max):
+    """``scipy.ndimage.maximum_filter(a, size)`` / ``minimum_filter(a, size)`` as fitting.py:95,102 call them (mode
+    'reflect', window ``[-(size // 2), size - size // 2 - 1]`` on every axis: lopsided for an even size).  Size 3 keeps the
+    NumPy restatement above; every other size goes through scipy.ndimage, whose max/min output is exact."""
+    if size == 3:
+        return maximum_filter3(a) if is_max else minimum_filter3(a)
+    from scipy.ndimage import maximum_filter, minimum_filter
+    return (maximum_filter if is_max else minimum_filter)(a, size)
+
+
 # ----------------------------------------------------------------------------------------------
 # (a6) correction_tools/filter.py:14-19
 # ----------------------------------------------------------------------------------------------
@@ -142,8 +153,6 @@ def get_seeds(im, max_num_seeds=None, th_seed=150, th_seed_per=95, use_percentil
     """fitting.py:20-154.  Returns (N,3) or (N,4) float64 [z,x,y(,h)], brightest first."""
     if not isinstance(im, np.ndarray):
         raise TypeError("image given should be a numpy.ndarray")
-    if int(filt_size) != 3:
-        raise NotImplementedError("oracle restates filt_size=3 only")
     if th_seed_per >= 100 or th_seed_per <= 50:
         use_percentile = False
     if sel_center is not None:                                                    # :56-68
@@ -165,9 +174,9 @@ def get_seeds(im, max_num_seeds=None, th_seed=150, th_seed_per=95, use_percentil
         th = th_seed
     niters = int(dynamic_niters) if use_dynamic_th else 1
     max_im = gaussian_filter(_im, gfilt_size) if gfilt_size else np.array(_im)     # :91-94
-    max_ft = maximum_filter3(max_im) == max_im                                     # :95
+    max_ft = _rank_filter(max_im, int(filt_size), True) == max_im                  # :95
     min_im = gaussian_filter(_im, background_gfilt_size) if background_gfilt_size else np.array(_im)
-    min_ft = minimum_filter3(min_im) != min_im                                     # :102
+    min_ft = _rank_filter(min_im, int(filt_size), False) != min_im                 # :102
     mask = max_ft & min_ft
     diff = max_im.astype(np.float32) - min_im.astype(np.float32)                   # :106
     size = np.array(_im.shape)
