@@ -140,7 +140,7 @@ def get_seed_points_base_v2(im_sm, gfilt_size=5, filt_size=3, th_seed=3., max_nu
         capacity, n, sd = 4096, C.c_int(0), C.c_double(0)
         while True:
             rows = np.empty((capacity, 4), dtype=np.float64)
-            rc = L.lib().ia3_fastfit_seeds_dev(stack._h, int(gfilt_size), 2 * pix, C.c_double(float(th_seed)),
+            rc = L.lib().ia3_fastfit_seeds_dev(stack._h, int(gfilt_size), 2 * pix, float(th_seed),
                                                0 if strong64 else 1, cut, L.dptr(rows), capacity, C.byref(n), C.byref(sd))
             if rc == L.IA3_ECAPACITY and n.value > capacity:
                 capacity = n.value
@@ -189,7 +189,7 @@ def gfit_fast(im_, X_, bk_f=0.1, reconstruct=False, plt_val=False, compare_with_
     coords = np.ascontiguousarray(X.T, dtype=np.int32)
     out = np.empty(12, dtype=np.float64)
     L.check(L.lib().ia3_fastfit_voxels(L.dptr(vals), L.ptr(coords), len(vals), _FAST_KINDS[im_.dtype],
-                                       C.c_double(float(bk_f)), L.dptr(out)))
+                                       float(bk_f), L.dptr(out)))
     if reconstruct:
         h, bk = out[0], out[4]
         a, b, c, d, e, f = out[5:11]
@@ -232,7 +232,7 @@ def fast_fit_big_image(im, centers_zxy, radius_fit=4, avoid_neigbors=True, recen
         else:
             extra = (None, None, None)
         L.check(L.lib().ia3_fastfit_moments_dev(stack._h, L.dptr(cen), n, r, 1 if avoid_neigbors else 0,
-                                                1 if recenter else 0, C.c_double(0.1), L.dptr(out), *extra))
+                                                1 if recenter else 0, 0.1, L.dptr(out), *extra))
         dtype = stack.dtype
     finally:
         if owned:

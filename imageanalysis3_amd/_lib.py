@@ -10,49 +10,30 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("IA3_LIB_PATH") or os.path.join(_HERE, "libia3.so")   # IA3_LIB_PATH: developer builds (scripts/ab_*)
 
+# the #defines of include/ia3.h, under the header's names
 IA3_U16, IA3_F32 = 0, 1
 IA3_OK, IA3_EINVAL, IA3_EHIP, IA3_ENOMEM, IA3_ECAPACITY, IA3_EUNSUPPORTED = 0, -1, -2, -3, -4, -5
-MODE_REFLECT, MODE_NEAREST, MODE_CONSTANT = 0, 1, 2
-BLUR_DIVIDE, BLUR_SUBTRACT = 0, 1                   # ia3_blurnorm2d modes
-BLUR_MAX_GB = 32                                    # IA3_BLUR_MAX_GB
-OFFSET_ALIGNMENT_TOOLS, OFFSET_FITTING_V4 = 0, 1    # fftalign_2d offset conventions
-
-EXPORTS = [
-    "ia3_init", "ia3_last_error", "ia3_version", "ia3_device_name", "ia3_sync", "ia3_stream",
-    "ia3_release_workspace", "ia3_workspace_stats", "ia3_seed_skip_stats", "ia3_seed_bg_stats", "ia3_prepare_depth", "ia3_col_guard", "ia3_col_weights", "ia3_profile_enable", "ia3_profile_collect", "ia3_set_tuning",
-    "ia3_stack_upload", "ia3_stack_alloc", "ia3_stack_load_file", "ia3_stack_wrap", "ia3_stack_download", "ia3_stack_info",
-    "ia3_stack_free",
-    "ia3_gaussian_filter", "ia3_gaussian_filter_dev", "ia3_gaussian_highpass", "ia3_gaussian_highpass_dev",
-    "ia3_remove_hot_pixels", "ia3_z_shift_correction", "ia3_illumination_correct", "ia3_bleedthrough_correct",
-    "ia3_dog_seed", "ia3_dog_seed_dev", "ia3_dog_filters_dev", "ia3_seed_in_distance",
-    "ia3_find_background", "ia3_find_background_dev", "ia3_local_background_dev",
-    "ia3_stack_deinterleave", "ia3_buffer_upload", "ia3_buffer_free", "ia3_remove_hot_pixels_dev",
-    "ia3_z_shift_correction_dev", "ia3_illumination_correct_dev", "ia3_bleedthrough_correct_dev",
-    "ia3_illumination_rescale_dev", "ia3_bleedthrough_rescale_dev",
-    "ia3_fit_create", "ia3_fit_first", "ia3_fit_repeat", "ia3_fit_run", "ia3_fit_results", "ia3_fit_results_ex", "ia3_fit_nfev", "ia3_fit_stats", "ia3_fit_counters",
-    "ia3_fit_snapshot", "ia3_fit_view_voxels", "ia3_fit_view_recs", "ia3_fit_view_residual", "ia3_fit_view_residual_dev",
-    "ia3_fit_create_fovs",
-    "ia3_fit_destroy", "ia3_fit_seeds", "ia3_fit_fov_dev", "ia3_fit_fov_stats", "ia3_fit_fov_wait_share", "ia3_fit_fovs",
-    "ia3_gaussfit_voxels",
-    "ia3_fftalign_2d", "ia3_fft3d_from2d", "ia3_fft3d_from2d_dev", "ia3_phase_xcorr3d", "ia3_phase_xcorr3d_dev",
-    "ia3_blurnorm2d", "ia3_fftalign_2d_ex", "ia3_fft3d_from2d_ex", "ia3_fft3d_from2d_dev_ex",
-    "ia3_stack_crop", "ia3_warp3d", "ia3_warp3d_dev",
-    "ia3_align_image_dev", "ia3_process_movies", "ia3_drift_ref_create", "ia3_drift_ref_free", "ia3_align_image_ref",
-    "ia3_stack_order_stats_dev", "ia3_stack_percentiles_dev", "ia3_clip_sum_z_dev",
-    "ia3_gaussian_filter2d_f64_dev", "ia3_gaussian_filter2d_f64", "ia3_illumination_image_profile_dev",
-    "ia3_crop_pairs_dev", "ia3_poly_field_dev", "ia3_buffer_alloc", "ia3_buffer_download", "ia3_bleedthrough_profile_dev",
-    "ia3_fastfit_normalize_dev", "ia3_fastfit_seeds_dev", "ia3_fastfit_moments_dev", "ia3_fastfit_voxels",
-    "ia3_label_boxes_dev", "ia3_cube_labels_dev", "ia3_cube_max_dev", "ia3_cube_gather_dev",
-    "ia3_plane_medians_dev", "ia3_chrom_seed_mask_dev", "ia3_binary_morph_dev", "ia3_binary_fill_holes_dev", "ia3_label_dev",
-    "ia3_label_centers_dev", "ia3_remove_small_labels_dev", "ia3_find_candidate_chromosomes_dev",
-    "ia3_chrom_image_create", "ia3_chrom_image_free", "ia3_chrom_image_upload", "ia3_chrom_image_download",
-    "ia3_chrom_image_add_dev", "ia3_stack_median_dev", "ia3_find_candidate_chromosomes_f64_dev",
-    "ia3_assign_nearest_dev", "ia3_select_chromosomes_dev",
-    "ia3_pick_create", "ia3_pick_free", "ia3_pick_by_intensity_dev", "ia3_pick_set_rows", "ia3_pick_reference_dev",
-    "ia3_pick_set_sorted", "ia3_pick_scores_dev", "ia3_pick_difference_dev", "ia3_pick_download", "ia3_pick_download_sorted",
-    "ia3_pick_cum_vals_dev",
-    "ia3_dist_create", "ia3_dist_free", "ia3_dist_summary_dev", "ia3_dist_contact_stack_dev",
-]
+IA3_MODE_REFLECT, IA3_MODE_NEAREST, IA3_MODE_CONSTANT = 0, 1, 2
+(IA3_TUNE_GAUSS_CERT, IA3_TUNE_DFT_VALU, IA3_TUNE_UPLOAD_THREADS, IA3_TUNE_SEED_DENSE, IA3_TUNE_FIT_NBLIST, IA3_TUNE_FFT_C2C,
+ IA3_TUNE_FIT_FUSE, IA3_TUNE_GAUSS_FOLD, IA3_TUNE_SEED_STRIPS, IA3_TUNE_FIT_WAVES, IA3_TUNE_FIT_MERGE, IA3_TUNE_WARP_ONEPASS,
+ IA3_TUNE_FIT_KDQ, IA3_TUNE_FIT_MEMO, IA3_TUNE_SEED_FUSED, IA3_TUNE_SEED_SKIP, IA3_TUNE_COL_RTC, IA3_TUNE_SEED_BGORDER,
+ IA3_TUNE_DIST_TILE) = range(1, 20)
+IA3_DEBUG_FIT_MAXFEV, IA3_DEBUG_FIT_WAITBOUND = 100, 101
+IA3_BLUR_MAX_GB = 32
+IA3_BLUR_DIVIDE, IA3_BLUR_SUBTRACT = 0, 1           # ia3_blurnorm2d modes
+IA3_OFFSET_ALIGNMENT_TOOLS, IA3_OFFSET_FITTING_V4 = 0, 1    # fftalign_2d offset conventions
+IA3_MORPH_ERODE, IA3_MORPH_DILATE, IA3_MORPH_CLOSE = 0, 1, 2   # ia3_binary_morph_dev operations
+IA3_SELECT_THREADS, IA3_SELECT_TILE = 256, 256      # spots of a workgroup, candidates of an LDS tile
+IA3_SELECT_EMPTY = 1                                # ia3_select_chromosomes_dev: every candidate was removed
+IA3_PICK_MAX_CHANNELS = 8
+IA3_MOVIE_MAXCH = 8
+# the names this module gave some of them before
+MODE_REFLECT, MODE_NEAREST, MODE_CONSTANT = IA3_MODE_REFLECT, IA3_MODE_NEAREST, IA3_MODE_CONSTANT
+BLUR_DIVIDE, BLUR_SUBTRACT, BLUR_MAX_GB = IA3_BLUR_DIVIDE, IA3_BLUR_SUBTRACT, IA3_BLUR_MAX_GB
+OFFSET_ALIGNMENT_TOOLS, OFFSET_FITTING_V4 = IA3_OFFSET_ALIGNMENT_TOOLS, IA3_OFFSET_FITTING_V4
+MORPH_ERODE, MORPH_DILATE, MORPH_CLOSE = IA3_MORPH_ERODE, IA3_MORPH_DILATE, IA3_MORPH_CLOSE
+SELECT_THREADS, SELECT_TILE = IA3_SELECT_THREADS, IA3_SELECT_TILE
+PICK_MAX_CHANNELS, MOVIE_MAXCH = IA3_PICK_MAX_CHANNELS, IA3_MOVIE_MAXCH
 
 
 class SeedParams(C.Structure):
@@ -88,9 +69,6 @@ class ChromParams(C.Structure):
     """ia3_chrom_params (include/ia3.h)."""
     _fields_ = [("filt_size", C.c_int), ("morphology_size", C.c_int), ("min_label_size", C.c_int),
                 ("binary_per_th", C.c_double)]
-
-
-MOVIE_MAXCH = 8
 
 
 class MovieParams(C.Structure):
@@ -129,15 +107,182 @@ class MovieJob(C.Structure):
                 ("stamps", C.c_double * 6)]
 
 
-_DP, _IP = C.POINTER(C.c_double), C.POINTER(C.c_int)
-# argument types of the ia3_dist_* entries as include/ia3.h declares them (an opaque handle is a void pointer)
-DIST_PROTOTYPES = {
-    "ia3_dist_create": (C.c_int, [_DP, _IP, C.c_int, C.POINTER(C.c_void_p)]),
-    "ia3_dist_free": (None, [C.c_void_p]),
-    "ia3_dist_summary_dev": (C.c_int, [C.c_void_p, _IP, _IP, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, _DP, _IP,
-                                       _IP]),
-    "ia3_dist_contact_stack_dev": (C.c_int, [_DP, C.c_longlong, C.c_longlong, C.c_double, _DP, _IP, _IP]),
+# Every entry of include/ia3.h: name -> (restype, [argtypes]); lib() declares them to ctypes.  A C type maps to ONE
+# ctypes type, here and in tests/test_abi_cpu.py, which reads the header:
+#   int, double, long long, size_t             c_int, c_double, c_longlong, c_size_t
+#   char*                                      c_char_p
+#   pointer to an arithmetic type              POINTER of its ctypes type (const ignored); uint8_t and unsigned char are
+#                                              c_ubyte; long long and int64_t are BOTH c_int64, the type of a NumPy int64
+#                                              array (c_longlong is another class of the same size on this platform)
+#   pointer to a parameter struct              POINTER of its mirror above
+#   void*, an opaque handle, T**               c_void_p
+assert C.sizeof(C.c_int64) == C.sizeof(C.c_longlong) == 8
+_I, _D, _LL, _SZ, _S, _H = C.c_int, C.c_double, C.c_longlong, C.c_size_t, C.c_char_p, C.c_void_p
+_DP, _IP, _FP, _BP = C.POINTER(C.c_double), C.POINTER(C.c_int), C.POINTER(C.c_float), C.POINTER(C.c_ubyte)
+_LP, _ULP = C.POINTER(C.c_int64), C.POINTER(C.c_uint64)
+_SEED, _FIT, _LSEED, _CHROM = C.POINTER(SeedParams), C.POINTER(FitParams), C.POINTER(LegacySeedParams), C.POINTER(ChromParams)
+_FOVJ, _MOVJ, _MOVP = C.POINTER(FovJob), C.POINTER(MovieJob), C.POINTER(MovieParams)
+PROTOTYPES = {
+    # runtime
+    "ia3_init": (_I, [_I]),
+    "ia3_last_error": (_S, []),
+    "ia3_version": (_S, []),
+    "ia3_device_name": (_I, [_S, _I]),
+    "ia3_sync": (_I, []),
+    "ia3_stream": (_H, []),
+    "ia3_release_workspace": (_I, []),
+    "ia3_prepare_depth": (_I, [_I, _I]),
+    "ia3_col_guard": (_I, [_I, _I, _I]),
+    "ia3_col_weights": (_I, [_I, _I, _I, _DP, _DP, _I]),
+    "ia3_workspace_stats": (_I, [_DP]),
+    "ia3_seed_skip_stats": (_I, [_DP]),
+    "ia3_seed_bg_stats": (_I, [_DP]),
+    "ia3_profile_enable": (_I, [_I]),
+    "ia3_profile_collect": (_I, [_S, _I]),
+    "ia3_set_tuning": (_I, [_I, _I]),
+    # device-resident stacks
+    "ia3_stack_upload": (_I, [_H, _I, _I, _I, _I, _H]),
+    "ia3_stack_alloc": (_I, [_I, _I, _I, _I, _H]),
+    "ia3_stack_load_file": (_I, [_S, _LL, _I, _I, _I, _I, _H]),
+    "ia3_stack_wrap": (_I, [_H, _I, _I, _I, _I, _H]),
+    "ia3_stack_deinterleave": (_I, [_H, _I, _I, _I, _H]),
+    "ia3_buffer_upload": (_I, [_H, _SZ, _H]),
+    "ia3_buffer_free": (None, [_H]),
+    "ia3_buffer_alloc": (_I, [_SZ, _H]),
+    "ia3_buffer_download": (_I, [_H, _SZ, _H]),
+    "ia3_stack_download": (_I, [_H, _H]),
+    "ia3_stack_info": (_I, [_H, _IP, _IP, _IP, _IP, _H]),
+    "ia3_stack_free": (None, [_H]),
+    # filters
+    "ia3_gaussian_filter": (_I, [_H, _I, _I, _I, _I, _D, _D, _I, _DP, _I, _H]),
+    "ia3_gaussian_filter_dev": (_I, [_H, _D, _D, _I, _DP, _I, _H]),
+    "ia3_gaussian_highpass": (_I, [_H, _I, _I, _I, _I, _D, _D, _DP, _I, _H]),
+    "ia3_gaussian_highpass_dev": (_I, [_H, _D, _D, _DP, _I, _H]),
+    "ia3_remove_hot_pixels": (_I, [_H, _I, _I, _I, _I, _D, _D, _H, _IP]),
+    "ia3_z_shift_correction": (_I, [_H, _I, _I, _I, _I, _H, _FP]),
+    "ia3_illumination_correct": (_I, [_H, _I, _I, _I, _H, _I, _H]),
+    "ia3_bleedthrough_correct": (_I, [_H, _I, _I, _I, _I, _H, _I, _H]),
+    # order statistics of a resident stack and illumination profiles
+    "ia3_stack_order_stats_dev": (_I, [_H, _LP, _I, _H]),
+    "ia3_stack_percentiles_dev": (_I, [_H, _DP, _I, _DP]),
+    "ia3_clip_sum_z_dev": (_I, [_H, _I, _D, _D, _DP]),
+    "ia3_gaussian_filter2d_f64_dev": (_I, [_DP, _I, _I, _D, _D, _I, _DP, _I, _DP]),
+    "ia3_gaussian_filter2d_f64": (_I, [_DP, _I, _I, _D, _D, _I, _DP, _I, _DP]),
+    "ia3_illumination_image_profile_dev": (_I, [_H, _I, _D, _D, _D, _DP, _I, _DP]),
+    # seeding
+    "ia3_dog_seed": (_I, [_H, _I, _I, _I, _I, _SEED, _DP, _I, _IP, _DP]),
+    "ia3_dog_seed_dev": (_I, [_H, _SEED, _DP, _I, _IP, _DP]),
+    "ia3_dog_filters_dev": (_I, [_H, _D, _D, _H, _H]),
+    # chromatic-aberration and bleedthrough profile generation
+    "ia3_crop_pairs_dev": (_I, [_H, _H, _DP, _DP, _I, _IP, _H, _H, _DP, _DP, _DP]),
+    "ia3_poly_field_dev": (_I, [_DP, _IP, _IP, _DP, _I, _I, _I, _I, _H]),
+    "ia3_bleedthrough_profile_dev": (_I, [_DP, _BP, _I, _I, _DP, _I, _I, _I, _I, _I, _I, _H, _LP]),
+    # the pre-correction chain on resident stacks
+    "ia3_remove_hot_pixels_dev": (_I, [_H, _D, _D, _I, _IP]),
+    "ia3_z_shift_correction_dev": (_I, [_H, _H]),
+    "ia3_illumination_correct_dev": (_I, [_H, _H, _I, _H]),
+    "ia3_bleedthrough_correct_dev": (_I, [_H, _I, _H, _I, _H]),
+    "ia3_illumination_rescale_dev": (_I, [_H, _H, _I, _I, _H]),
+    "ia3_bleedthrough_rescale_dev": (_I, [_H, _I, _H, _I, _I, _H]),
+    # background level
+    "ia3_find_background": (_I, [_H, _I, _I, _I, _I, _DP, _I, _I, _DP]),
+    "ia3_find_background_dev": (_I, [_H, _DP, _I, _I, _DP]),
+    "ia3_local_background_dev": (_I, [_H, _FP, _I, _I, _DP, _I, _I, _DP]),
+    # legacy per-cell seeding
+    "ia3_seed_in_distance": (_I, [_H, _I, _I, _I, _I, _DP, _LSEED, _LP, _I, _IP]),
+    # fitting
+    "ia3_fit_create": (_I, [_H, _DP, _I, _FIT, _H]),
+    "ia3_fit_first": (_I, [_H]),
+    "ia3_fit_repeat": (_I, [_H, _IP]),
+    "ia3_fit_run": (_I, [_H]),
+    "ia3_fit_results": (_I, [_H, _FP, _BP, _IP]),
+    "ia3_fit_results_ex": (_I, [_H, _FP, _BP, _IP, _IP]),
+    "ia3_fit_nfev": (_I, [_H, _IP]),
+    "ia3_fit_stats": (_I, [_H, _LP, _LP]),
+    "ia3_fit_counters": (_I, [_H, _ULP]),
+    "ia3_fit_destroy": (None, [_H]),
+    # views of a finished fit
+    "ia3_fit_snapshot": (_I, [_H]),
+    "ia3_fit_view_voxels": (_I, [_H, _IP, _IP, _DP]),
+    "ia3_fit_view_recs": (_I, [_H, _I, _IP, _BP, _DP, _DP]),
+    "ia3_fit_view_residual": (_I, [_H, _I, _DP]),
+    "ia3_fit_view_residual_dev": (_I, [_H, _I, _H]),
+    "ia3_fit_create_fovs": (_I, [_H, _H, _IP, _I, _FIT, _H]),
+    "ia3_gaussfit_voxels": (_I, [_DP, _IP, _IP, _I, _DP, _DP, _IP, _FP, _DP, _IP]),
+    "ia3_fit_seeds": (_I, [_H, _I, _I, _I, _I, _DP, _I, _FIT, _FP, _BP, _IP]),
+    "ia3_fit_fov_dev": (_I, [_H, _SEED, _FIT, _FP, _I, _IP, _IP, _IP]),
+    "ia3_fit_fov_stats": (_I, [_LP, _LP, _LP]),
+    "ia3_fit_fov_wait_share": (_I, [_LP, _LP]),
+    "ia3_fit_fovs": (_I, [_FOVJ, _I, _I, _I, _I, _I, _SEED, _FIT, _I]),
+    # drift
+    "ia3_fftalign_2d": (_I, [_DP, _I, _I, _DP, _I, _I, _DP, _D, _IP]),
+    "ia3_fft3d_from2d": (_I, [_H, _H, _I, _I, _I, _I, _D, _IP]),
+    "ia3_fft3d_from2d_dev": (_I, [_H, _H, _D, _IP]),
+    "ia3_blurnorm2d": (_I, [_FP, _I, _I, _I, _I, _FP]),
+    "ia3_fftalign_2d_ex": (_I, [_DP, _I, _I, _DP, _I, _I, _DP, _D, _I, _IP, _DP]),
+    "ia3_fft3d_from2d_ex": (_I, [_H, _H, _I, _I, _I, _I, _I, _I, _I, _D, _IP, _DP]),
+    "ia3_fft3d_from2d_dev_ex": (_I, [_H, _H, _I, _I, _I, _D, _IP, _DP]),
+    "ia3_phase_xcorr3d": (_I, [_H, _H, _I, _I, _I, _I, _I, _I, _DP, _DP, _DP]),
+    "ia3_phase_xcorr3d_dev": (_I, [_H, _H, _I, _I, _DP, _DP, _DP]),
+    "ia3_align_image_dev": (_I, [_H, _H, _IP, _I, _I, _I, _I, _D, _DP, _IP, _DP, _IP]),
+    "ia3_drift_ref_create": (_I, [_H, _IP, _I, _H]),
+    "ia3_drift_ref_free": (None, [_H]),
+    "ia3_align_image_ref": (_I, [_H, _H, _I, _I, _I, _D, _DP, _IP, _DP, _IP]),
+    # Fitting_v4's fast path
+    "ia3_fastfit_normalize_dev": (_I, [_H, _I, _H]),
+    "ia3_fastfit_seeds_dev": (_I, [_H, _I, _I, _D, _I, _I, _DP, _I, _IP, _DP]),
+    "ia3_fastfit_moments_dev": (_I, [_H, _DP, _I, _I, _I, _I, _D, _DP, _IP, _DP, _IP]),
+    "ia3_fastfit_voxels": (_I, [_DP, _IP, _I, _I, _D, _DP]),
+    # warp
+    "ia3_warp3d": (_I, [_H, _I, _I, _I, _I, _DP, _H, _I, _I, _I, _D, _H]),
+    "ia3_warp3d_dev": (_I, [_H, _DP, _H, _I, _I, _I, _D, _H]),
+    "ia3_stack_crop": (_I, [_H, _I, _I, _I, _I, _I, _I, _H]),
+    # segmentation label images
+    "ia3_label_boxes_dev": (_I, [_H, _I, _IP]),
+    "ia3_cube_labels_dev": (_I, [_H, _DP, _I, _I, _IP, _IP]),
+    "ia3_cube_max_dev": (_I, [_H, _DP, _I, _I, _H]),
+    "ia3_cube_gather_dev": (_I, [_H, _DP, _I, _I, _H]),
+    # candidate chromosomes
+    "ia3_plane_medians_dev": (_I, [_H, _DP]),
+    "ia3_chrom_seed_mask_dev": (_I, [_H, _I, _D, _H, _DP]),
+    "ia3_binary_morph_dev": (_I, [_H, _I, _I, _I, _H]),
+    "ia3_binary_fill_holes_dev": (_I, [_H, _H]),
+    "ia3_label_dev": (_I, [_H, _IP, _IP, _H]),
+    "ia3_label_centers_dev": (_I, [_H, _I, _I, _I, _I, _I, _DP, _LP]),
+    "ia3_remove_small_labels_dev": (_I, [_H, _I, _I, _I, _I, _I, _LL, _H]),
+    "ia3_find_candidate_chromosomes_dev": (_I, [_H, _CHROM, _DP, _I, _IP, _DP, _H]),
+    # the chromosome image
+    "ia3_chrom_image_create": (_I, [_I, _I, _I, _H]),
+    "ia3_chrom_image_free": (None, [_H]),
+    "ia3_chrom_image_upload": (_I, [_H, _DP]),
+    "ia3_chrom_image_download": (_I, [_H, _DP]),
+    "ia3_stack_median_dev": (_I, [_H, _DP]),
+    "ia3_chrom_image_add_dev": (_I, [_H, _H, _IP, _IP, _I, _DP]),
+    "ia3_find_candidate_chromosomes_f64_dev": (_I, [_H, _CHROM, _DP, _I, _IP, _DP, _H]),
+    # chromosome selection by candidate spots
+    "ia3_assign_nearest_dev": (_I, [_DP, _I, _DP, _I, _IP]),
+    "ia3_select_chromosomes_dev": (_I, [_DP, _IP, _I, _DP, _I, _D, _IP, _IP, _IP, _IP, _IP, _LP, _DP]),
+    # population spot picking
+    "ia3_pick_create": (_I, [_DP, _I, _IP, _BP, _I, _I, _IP, _I, _H]),
+    "ia3_pick_free": (None, [_H]),
+    "ia3_pick_by_intensity_dev": (_I, [_H]),
+    "ia3_pick_set_rows": (_I, [_H, _I, _DP]),
+    "ia3_pick_reference_dev": (_I, [_H, _IP, _IP, _I, _DP, _I, _IP]),
+    "ia3_pick_set_sorted": (_I, [_H, _I, _I, _DP, _I]),
+    "ia3_pick_scores_dev": (_I, [_H, _IP, _IP, _I, _I, _D, _D, _DP, _I, _H, _IP, _I]),
+    "ia3_pick_difference_dev": (_I, [_H, _IP]),
+    "ia3_pick_download": (_I, [_H, _I, _H]),
+    "ia3_pick_download_sorted": (_I, [_H, _I, _I, _DP]),
+    "ia3_pick_cum_vals_dev": (_I, [_DP, _I, _DP, _I, _IP]),
+    # summaries of population distance maps
+    "ia3_dist_create": (_I, [_DP, _IP, _I, _H]),
+    "ia3_dist_free": (None, [_H]),
+    "ia3_dist_summary_dev": (_I, [_H, _IP, _IP, _I, _I, _I, _I, _I, _D, _DP, _IP, _IP]),
+    "ia3_dist_contact_stack_dev": (_I, [_DP, _LL, _LL, _D, _DP, _IP, _IP]),
+    # whole round-folder movies
+    "ia3_process_movies": (_I, [_MOVJ, _I, _MOVP]),
 }
+EXPORTS = list(PROTOTYPES)
 
 _lib = None
 
@@ -154,15 +299,7 @@ def lib():
         # environment before the HIP runtime starts, hence also here, before anything is loaded
         os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
         L = C.CDLL(LIB_PATH)
-        L.ia3_last_error.restype = C.c_char_p
-        L.ia3_version.restype = C.c_char_p
-        L.ia3_stream.restype = C.c_void_p
-        L.ia3_stack_free.restype = None
-        L.ia3_fit_destroy.restype = None
-        L.ia3_drift_ref_free.restype = None
-        L.ia3_chrom_image_free.restype = None
-        L.ia3_pick_free.restype = None
-        for name, (res, args) in DIST_PROTOTYPES.items():
+        for name, (res, args) in PROTOTYPES.items():
             fn = getattr(L, name)
             fn.restype, fn.argtypes = res, args
         _lib = L
@@ -207,14 +344,43 @@ def as_stack_array(im):
 
 
 def ptr(a):
-    return a.ctypes.data_as(C.c_void_p)
+    """Pointer to the data of an ndarray, typed by its dtype (float64: ``double*``, int32: ``int*``, ...): an entry that
+    declares another element type refuses it.  An array that is to be read as another type says so with ``.view()``."""
+    return a.ctypes.data_as(C.POINTER(np.ctypeslib.as_ctypes_type(a.dtype)))
 
 
-def dptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_double))
+dptr = _iptr = ptr   # the names callers used before the pointer carried the dtype
 
 
-class DeviceStack(object):
+class Owner(object):
+    """Base of the classes that own one library handle: ``_release(handle)`` hands it to the entry that frees it,
+    ``_handle`` names the attribute that holds it (None once it is freed; absent when ``__init__`` never got that far)."""
+    _handle = "_h"
+
+    def _release(self, handle):
+        raise NotImplementedError
+
+    def free(self):
+        h = getattr(self, self._handle, None)
+        if h is not None:
+            setattr(self, self._handle, None)
+            self._keep = None
+            self._release(h)
+
+    def __del__(self):
+        try:
+            self.free()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *a):
+        self.free()
+
+
+class DeviceStack(Owner):
     """A (Z,X,Y) stack resident in HBM (owner of an ``ia3_stack`` handle)."""
 
     def __init__(self, handle, shape, dtype, keepalive=None):
@@ -260,7 +426,7 @@ class DeviceStack(object):
         """Resident uint16 (frames, X, Y) stack read straight from a raw movie file (pipelined read + upload)."""
         import os
         h = C.c_void_p()
-        check(lib().ia3_stack_load_file(os.fsencode(path), C.c_longlong(int(offset_bytes)), int(frames), int(X), int(Y),
+        check(lib().ia3_stack_load_file(os.fsencode(path), int(offset_bytes), int(frames), int(X), int(Y),
                                         1 if big_endian else 0, C.byref(h)))
         return cls(h, (int(frames), int(X), int(Y)), np.dtype(np.uint16))
 
@@ -283,7 +449,7 @@ class DeviceStack(object):
         """``np.sort(stack, axis=None)[ranks]`` (at most 16 ranks) selected on the device: array of the stack dtype."""
         r = np.ascontiguousarray(ranks, dtype=np.int64).ravel()
         out = np.empty(len(r), dtype=self.dtype)
-        check(lib().ia3_stack_order_stats_dev(self._h, r.ctypes.data_as(C.POINTER(C.c_longlong)), len(r), ptr(out)))
+        check(lib().ia3_stack_order_stats_dev(self._h, ptr(r), len(r), ptr(out)))
         return out
 
     def percentiles(self, pers):
@@ -291,31 +457,17 @@ class DeviceStack(object):
         on the device: float64 array."""
         p = np.ascontiguousarray(pers, dtype=np.float64).ravel()
         out = np.empty(len(p), dtype=np.float64)
-        check(lib().ia3_stack_percentiles_dev(self._h, dptr(p), len(p), dptr(out)))
+        check(lib().ia3_stack_percentiles_dev(self._h, ptr(p), len(p), ptr(out)))
         return out
 
-    def free(self):
-        if self._h is not None:
-            lib().ia3_stack_free(self._h)
-            self._h = None
-            self._keep = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.free()
+    def _release(self, handle):
+        lib().ia3_stack_free(handle)
 
 
 class DeviceImage64(object):
     """A float64 (X, Y) image resident in HBM (what ``ia3_clip_sum_z_dev`` writes and ``ia3_gaussian_filter2d_f64_dev``
-    reads and writes), kept in a library allocation of the same size."""
+    reads and writes), kept in a library allocation of the same size.  ``devptr`` is the device address as a ``double*``
+    (``POINTER(c_double)``, what those entries declare), not a ``c_void_p``."""
 
     def __init__(self, shape, _store=None):
         self.shape = (int(shape[0]), int(shape[1]))
@@ -323,7 +475,7 @@ class DeviceImage64(object):
         self._store = DeviceStack.empty((2,) + self.shape, np.float32) if _store is None else _store
         d = C.c_void_p()
         check(lib().ia3_stack_info(self._store._h, None, None, None, None, C.byref(d)))
-        self.devptr = C.c_void_p(d.value)
+        self.devptr = C.cast(d, _DP)
 
     @classmethod
     def upload(cls, im):
@@ -352,7 +504,7 @@ def clip_sum_z(stack, limits=None):
     out = DeviceImage64(stack.shape[1:])
     lo, hi = (0.0, 0.0) if limits is None else (float(limits[0]), float(limits[1]))
     try:
-        check(lib().ia3_clip_sum_z_dev(stack._h, 0 if limits is None else 1, C.c_double(lo), C.c_double(hi), out.devptr))
+        check(lib().ia3_clip_sum_z_dev(stack._h, 0 if limits is None else 1, lo, hi, out.devptr))
     except Exception:
         out.free()
         raise
@@ -366,7 +518,7 @@ def taps_argument(sigma, truncate=4.0, max_radius=1024):
     if not (sigma > 0 and truncate > 0) or truncate * sigma + 0.5 >= max_radius + 1:
         return None, 0, None
     w, r = gaussian_taps(sigma, truncate)
-    return dptr(w), int(r), w
+    return ptr(w), int(r), w
 
 
 def gaussian_filter2d_f64(im, sigma, truncate=4.0, mode=MODE_REFLECT):
@@ -376,8 +528,8 @@ def gaussian_filter2d_f64(im, sigma, truncate=4.0, mode=MODE_REFLECT):
     if isinstance(im, DeviceImage64):
         out = DeviceImage64(im.shape)
         try:
-            check(lib().ia3_gaussian_filter2d_f64_dev(im.devptr, im.shape[0], im.shape[1], C.c_double(float(sigma)),
-                                                      C.c_double(float(truncate)), int(mode), wp, r, out.devptr))
+            check(lib().ia3_gaussian_filter2d_f64_dev(im.devptr, im.shape[0], im.shape[1], float(sigma),
+                                                      float(truncate), int(mode), wp, r, out.devptr))
         except Exception:
             out.free()
             raise
@@ -386,8 +538,8 @@ def gaussian_filter2d_f64(im, sigma, truncate=4.0, mode=MODE_REFLECT):
     if a.ndim != 2:
         raise IndexError("a 2-D image is required, got ndim=%d" % a.ndim)
     out = np.empty_like(a)
-    check(lib().ia3_gaussian_filter2d_f64(dptr(a), a.shape[0], a.shape[1], C.c_double(float(sigma)),
-                                          C.c_double(float(truncate)), int(mode), wp, r, dptr(out)))
+    check(lib().ia3_gaussian_filter2d_f64(ptr(a), a.shape[0], a.shape[1], float(sigma),
+                                          float(truncate), int(mode), wp, r, ptr(out)))
     return out
 
 
@@ -414,16 +566,14 @@ def crop_pairs(stack_a, centers_a, crop, stack_b=None, centers_b=None, regress=F
         boxes_b = np.empty(shape, dtype=stack_b.dtype)
     if regress:
         reg = tuple(np.empty(n, dtype=np.float64) for _ in range(3))
-    check(lib().ia3_crop_pairs_dev(stack_a._h, None if stack_b is None else stack_b._h, dptr(ca),
-                                   None if cb is None else dptr(cb), n, crop.ctypes.data_as(C.POINTER(C.c_int)),
+    check(lib().ia3_crop_pairs_dev(stack_a._h, None if stack_b is None else stack_b._h, ptr(ca),
+                                   None if cb is None else ptr(cb), n, ptr(crop),
                                    ptr(boxes_a), None if boxes_b is None else ptr(boxes_b),
-                                   *([dptr(r) for r in reg] if regress else [None, None, None])))
+                                   *([ptr(r) for r in reg] if regress else [None, None, None])))
     return boxes_a, boxes_b, reg
 
 
 CUBE_MAX_RADIUS = 10          # largest search radius of the cube lookups (csrc/ia3_labels.h)
-IA3_TUNE_COL_RTC = 17
-IA3_TUNE_DIST_TILE = 19
 
 
 def _centres(centers_zxy):
@@ -438,7 +588,7 @@ def label_boxes(labels, max_label=65535):
     """``ia3_label_boxes_dev``: the (max_label + 1, 7) int32 table [count, z0, z1, x0, x1, y0, y1] of a resident uint16
     label stack, row l for label l ([start, stop) bounds without a margin; zeros for a label that does not occur)."""
     out = np.empty((int(max_label) + 1, 7), dtype=np.int32)
-    check(lib().ia3_label_boxes_dev(labels._h, int(max_label), out.ctypes.data_as(C.POINTER(C.c_int))))
+    check(lib().ia3_label_boxes_dev(labels._h, int(max_label), ptr(out)))
     return out
 
 
@@ -452,9 +602,8 @@ def cube_labels(labels, centers_zxy, radius, target=None):
         t = np.ascontiguousarray(target, dtype=np.int32).ravel()
         if len(t) != len(c):
             raise ValueError("cube_labels: %d centres, %d target labels" % (len(c), len(t)))
-    check(lib().ia3_cube_labels_dev(labels._h, dptr(c), len(c), int(radius),
-                                    None if t is None else t.ctypes.data_as(C.POINTER(C.c_int)),
-                                    out.ctypes.data_as(C.POINTER(C.c_int))))
+    check(lib().ia3_cube_labels_dev(labels._h, ptr(c), len(c), int(radius),
+                                    None if t is None else ptr(t), ptr(out)))
     return out
 
 
@@ -463,7 +612,7 @@ def cube_max(stack, centers_zxy, radius):
     (NaN where a float32 cube holds one)."""
     c = _centres(centers_zxy)
     out = np.empty(len(c), dtype=stack.dtype)
-    check(lib().ia3_cube_max_dev(stack._h, dptr(c), len(c), int(radius), ptr(out)))
+    check(lib().ia3_cube_max_dev(stack._h, ptr(c), len(c), int(radius), ptr(out)))
     return out
 
 
@@ -472,11 +621,10 @@ def cube_gather(stack, centers_zxy, radius):
     order of the offsets (dz, dx, dy)."""
     c = _centres(centers_zxy)
     out = np.empty((len(c), (2 * int(radius) + 1) ** 3), dtype=stack.dtype)
-    check(lib().ia3_cube_gather_dev(stack._h, dptr(c), len(c), int(radius), ptr(out)))
+    check(lib().ia3_cube_gather_dev(stack._h, ptr(c), len(c), int(radius), ptr(out)))
     return out
 
 
-MORPH_ERODE, MORPH_DILATE, MORPH_CLOSE = 0, 1, 2   # ia3_binary_morph_dev operations
 MORPH_MAX_RADIUS = 2                               # largest ball of the bit-row operators
 CHROM_FILT_SIZES = (1, 5)                          # _filt_size range of the range filter
 MAX_LABELS16 = 65535
@@ -489,15 +637,16 @@ def stack_devptr(stack):
     return C.c_void_p(d.value)
 
 
-class DeviceLabels(object):
+class DeviceLabels(Owner):
     """int32 labels of a (Z, X, Y) volume in a device buffer (what ``ia3_label_dev`` writes); ``n`` = number of labels."""
+    _handle = "devptr"
 
     def __init__(self, shape, n=0):
         self.shape = tuple(int(v) for v in shape)
         self.dtype = np.dtype(np.int32)
         self.n = int(n)
         p = C.c_void_p()
-        check(lib().ia3_buffer_alloc(C.c_size_t(4 * int(np.prod(self.shape))), C.byref(p)))
+        check(lib().ia3_buffer_alloc(4 * int(np.prod(self.shape)), C.byref(p)))
         self.devptr = p
 
     @classmethod
@@ -509,37 +658,23 @@ class DeviceLabels(object):
         out.shape, out.dtype = tuple(a.shape), np.dtype(np.int32)
         out.n = int(a.max()) if n is None and a.size else int(n or 0)
         p = C.c_void_p()
-        check(lib().ia3_buffer_upload(ptr(a), C.c_size_t(a.nbytes), C.byref(p)))
+        check(lib().ia3_buffer_upload(ptr(a), a.nbytes, C.byref(p)))
         out.devptr = p
         return out
 
     def download(self):
         out = np.empty(self.shape, dtype=np.int32)
-        check(lib().ia3_buffer_download(self.devptr, C.c_size_t(out.nbytes), ptr(out)))
+        check(lib().ia3_buffer_download(self.devptr, out.nbytes, ptr(out)))
         return out
 
-    def free(self):
-        if self.devptr is not None:
-            lib().ia3_buffer_free(self.devptr)
-            self.devptr = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.free()
+    def _release(self, handle):
+        lib().ia3_buffer_free(handle)
 
 
 def plane_medians(stack):
     """``ia3_plane_medians_dev``: ``[np.median(plane) for plane in stack]`` of a resident stack, widened to float64."""
     out = np.empty(stack.shape[0], dtype=np.float64)
-    check(lib().ia3_plane_medians_dev(stack._h, dptr(out)))
+    check(lib().ia3_plane_medians_dev(stack._h, ptr(out)))
     return out
 
 
@@ -548,7 +683,7 @@ def chrom_seed_mask(stack, filt_size, binary_per_th):
     out = DeviceStack.empty(stack.shape, np.uint16)
     th = C.c_double(0)
     try:
-        check(lib().ia3_chrom_seed_mask_dev(stack._h, int(filt_size), C.c_double(float(binary_per_th)), out._h, C.byref(th)))
+        check(lib().ia3_chrom_seed_mask_dev(stack._h, int(filt_size), float(binary_per_th), out._h, C.byref(th)))
     except Exception:
         out.free()
         raise
@@ -584,7 +719,7 @@ def label(mask, labels16=False):
     out16 = DeviceStack.empty(mask.shape, np.uint16) if labels16 else None
     n = C.c_int(0)
     try:
-        check(lib().ia3_label_dev(mask._h, lab.devptr, C.byref(n), None if out16 is None else out16._h))
+        check(lib().ia3_label_dev(mask._h, C.cast(lab.devptr, _IP), C.byref(n), None if out16 is None else out16._h))
     except Exception:
         lab.free()
         if out16 is not None:
@@ -610,8 +745,7 @@ def label_centers(labels, max_label):
     max_label = int(max_label)
     cen = np.empty((max_label, 3), dtype=np.float64)
     cnt = np.empty(max_label, dtype=np.int64)
-    check(lib().ia3_label_centers_dev(p, bits, shape[0], shape[1], shape[2], max_label, dptr(cen),
-                                      cnt.ctypes.data_as(C.POINTER(C.c_longlong))))
+    check(lib().ia3_label_centers_dev(p, bits, shape[0], shape[1], shape[2], max_label, ptr(cen), ptr(cnt)))
     return cen, cnt
 
 
@@ -621,7 +755,7 @@ def remove_small_labels(labels, max_label, min_size):
     p, bits, shape = _label_volume(labels)
     out = DeviceLabels(shape, labels.n) if bits == 32 else DeviceStack.empty(shape, np.uint16)
     try:
-        check(lib().ia3_remove_small_labels_dev(p, bits, shape[0], shape[1], shape[2], int(max_label), C.c_longlong(int(min_size)),
+        check(lib().ia3_remove_small_labels_dev(p, bits, shape[0], shape[1], shape[2], int(max_label), int(min_size),
                                                 out.devptr if bits == 32 else stack_devptr(out)))
     except Exception:
         out.free()
@@ -639,7 +773,7 @@ def stack_median(stack):
     return np.float64(out.value)
 
 
-class ChromImage(object):
+class ChromImage(Owner):
     """A float64 (Z, X, Y) volume resident in HBM (owner of an ``ia3_chrom_image`` handle): the chromosome image that
     ``Field_of_View._generate_chrom_im_from_data`` sums up, and what ``find_candidate_chromosomes`` reads in float64."""
 
@@ -670,7 +804,7 @@ class ChromImage(object):
         a = np.ascontiguousarray(im)
         out = cls.empty(a.shape)
         try:
-            check(lib().ia3_chrom_image_upload(out._h, dptr(a)))
+            check(lib().ia3_chrom_image_upload(out._h, ptr(a)))
         except Exception:
             out.free()
             raise
@@ -678,7 +812,7 @@ class ChromImage(object):
 
     def download(self):
         out = np.empty(self.shape, dtype=np.float64)
-        check(lib().ia3_chrom_image_download(self._h, dptr(out)))
+        check(lib().ia3_chrom_image_download(self._h, ptr(out)))
         return out
 
     def add(self, stacks, flags, shifts):
@@ -695,26 +829,11 @@ class ChromImage(object):
         if n == 0:
             return bg
         hs = (C.c_void_p * n)(*[s._h for s in stacks])
-        check(lib().ia3_chrom_image_add_dev(self._h, hs, fl.ctypes.data_as(C.POINTER(C.c_int)),
-                                            sh.ctypes.data_as(C.POINTER(C.c_int)), n, dptr(bg)))
+        check(lib().ia3_chrom_image_add_dev(self._h, hs, ptr(fl), ptr(sh), n, ptr(bg)))
         return bg
 
-    def free(self):
-        if self._h is not None:
-            lib().ia3_chrom_image_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.free()
+    def _release(self, handle):
+        lib().ia3_chrom_image_free(handle)
 
 
 def find_candidate_chromosomes(stack, filt_size, binary_per_th, morphology_size, min_label_size, return_label=False,
@@ -729,7 +848,7 @@ def find_candidate_chromosomes(stack, filt_size, binary_per_th, morphology_size,
     try:
         while True:
             coords = np.empty((capacity, 3), dtype=np.float64)
-            rc = entry(stack._h, C.byref(p), dptr(coords), int(capacity), C.byref(n),
+            rc = entry(stack._h, C.byref(p), ptr(coords), int(capacity), C.byref(n),
                        C.byref(th), None if kept is None else kept._h)
             if rc == IA3_ECAPACITY and n.value > capacity:
                 capacity = n.value
@@ -741,14 +860,6 @@ def find_candidate_chromosomes(stack, filt_size, binary_per_th, morphology_size,
             kept.free()
         raise
     return coords[:n.value].copy(), np.float64(th.value), kept
-
-
-SELECT_THREADS, SELECT_TILE = 256, 256   # IA3_SELECT_THREADS, IA3_SELECT_TILE: spots of a workgroup, candidates of an LDS tile
-IA3_SELECT_EMPTY = 1                     # ia3_select_chromosomes_dev: every candidate was removed
-
-
-def _iptr(a):
-    return a.ctypes.data_as(C.POINTER(C.c_int))
 
 
 def _scaled_table(zxy, what):
@@ -764,7 +875,7 @@ def assign_nearest(spots_zxy, cands_zxy):
     (``np.argmin(cdist(spots_zxy, cands_zxy), axis=1)``, int32)."""
     s, c = _scaled_table(spots_zxy, "spots"), _scaled_table(cands_zxy, "candidates")
     owner = np.empty(len(s), dtype=np.int32)
-    check(lib().ia3_assign_nearest_dev(dptr(s), len(s), dptr(c), len(c), _iptr(owner)))
+    check(lib().ia3_assign_nearest_dev(ptr(s), len(s), ptr(c), len(c), ptr(owner)))
     return owner
 
 
@@ -780,11 +891,11 @@ def select_chromosomes(spots_zxy, round_start, cands_zxy, loss_th, return_owner=
     removed, removed_lost = np.empty(len(c), dtype=np.int32), np.empty(len(c), dtype=np.int32)
     lost = np.empty(len(c), dtype=np.int32)
     owner = np.empty(len(s), dtype=np.int32) if return_owner else None
-    n, visits, t = C.c_int(0), C.c_longlong(0), np.zeros(3, dtype=np.float64)
-    rc = check(lib().ia3_select_chromosomes_dev(dptr(s), _iptr(rs), len(rs) - 1, dptr(c), len(c), C.c_double(float(loss_th)),
-                                                _iptr(removed), _iptr(removed_lost), C.byref(n), _iptr(lost),
-                                                None if owner is None else _iptr(owner), C.byref(visits),
-                                                dptr(t) if times else None), allow=(IA3_SELECT_EMPTY,))
+    n, visits, t = C.c_int(0), C.c_int64(0), np.zeros(3, dtype=np.float64)
+    rc = check(lib().ia3_select_chromosomes_dev(ptr(s), ptr(rs), len(rs) - 1, ptr(c), len(c), float(loss_th),
+                                                ptr(removed), ptr(removed_lost), C.byref(n), ptr(lost),
+                                                None if owner is None else ptr(owner), C.byref(visits),
+                                                ptr(t) if times else None), allow=(IA3_SELECT_EMPTY,))
     removed, removed_lost = removed[:n.value].copy(), removed_lost[:n.value].copy()
     lost[removed] = removed_lost
     out = dict(removed=removed, removed_lost=removed_lost, lost=lost, visits=int(visits.value),
@@ -796,7 +907,6 @@ def select_chromosomes(spots_zxy, round_start, cands_zxy, loss_th, return_owner=
     return out
 
 
-PICK_MAX_CHANNELS = 8                    # IA3_PICK_MAX_CHANNELS
 PICK_KEYS = PICK_MAX_CHANNELS + 1        # keys per kind in the flat [kind][key] tables of ia3_pick_*
 PICK_KINDS = ("ct", "lc", "int")         # kind 0, 1, 2: centre distance, local-centre distance, intensity
 PICK_ROWS_PICKS, PICK_ROWS_PREV, PICK_ROWS_REF = 0, 1, 2
@@ -812,7 +922,7 @@ def cum_vals(sorted_vals, targets):
     if len(v) == 0:
         raise IndexError("index 0 is out of bounds for axis 0 with size 0")
     mids = np.empty(len(t), dtype=np.int32)
-    check(lib().ia3_pick_cum_vals_dev(dptr(v), len(v), dptr(t), len(t), _iptr(mids)))
+    check(lib().ia3_pick_cum_vals_dev(ptr(v), len(v), ptr(t), len(t), ptr(mids)))
     return mids
 
 
@@ -857,7 +967,7 @@ def pick_log_tables(n):
         return np.log(v), np.log(1 - v)
 
 
-class PickPopulation(object):
+class PickPopulation(Owner):
     """A population of P chromosomes x R regions with its candidate spots resident in HBM (owner of an
     ``ia3_pick_population`` handle), and on it the steps of the reference's population picker (picking.py:1567-2342).
     Keys of the reference arrays are channel numbers ``0..n_channels-1`` and ``n_channels`` for 'all'."""
@@ -884,8 +994,8 @@ class PickPopulation(object):
             if len(ch) != R:
                 raise ValueError("PickPopulation.upload: %d channels for %d regions" % (len(ch), R))
         h = C.c_void_p()
-        check(lib().ia3_pick_create(dptr(t), len(t), _iptr(rs), fl.ctypes.data_as(C.POINTER(C.c_ubyte)), P, R,
-                                    None if ch is None else _iptr(ch), int(n_channels) if ch is not None else 0, C.byref(h)))
+        check(lib().ia3_pick_create(ptr(t), len(t), ptr(rs), ptr(fl), P, R,
+                                    None if ch is None else ptr(ch), int(n_channels) if ch is not None else 0, C.byref(h)))
         return cls(h, P, R, len(t), int(n_channels) if ch is not None else 0)
 
     def _rows(self, rows):
@@ -895,7 +1005,7 @@ class PickPopulation(object):
         return t
 
     def set_rows(self, which, rows):
-        check(lib().ia3_pick_set_rows(self._h, int(which), dptr(self._rows(rows))))
+        check(lib().ia3_pick_set_rows(self._h, int(which), ptr(self._rows(rows))))
 
     def pick_by_intensity(self):
         check(lib().ia3_pick_by_intensity_dev(self._h))
@@ -921,14 +1031,14 @@ class PickPopulation(object):
         ws, wi = self._window(win_start, win_idx, self.R)
         c = self._centers(centers)
         lengths = np.full((3, PICK_KEYS), -1, dtype=np.int32)
-        check(lib().ia3_pick_reference_dev(self._h, _iptr(ws), _iptr(wi), 1 if split else 0, None if c is None else dptr(c),
-                                           1 if ref_is_picks else 0, _iptr(lengths)))
+        check(lib().ia3_pick_reference_dev(self._h, ptr(ws), ptr(wi), 1 if split else 0, None if c is None else ptr(c),
+                                           1 if ref_is_picks else 0, ptr(lengths)))
         self.lengths = lengths
         return lengths
 
     def set_sorted(self, kind, key, values):
         v = np.ascontiguousarray(values, dtype=np.float64).ravel()
-        check(lib().ia3_pick_set_sorted(self._h, int(kind), int(key), dptr(v), len(v)))
+        check(lib().ia3_pick_set_sorted(self._h, int(kind), int(key), ptr(v), len(v)))
         self.lengths[kind, key] = len(v)
 
     def scores(self, win_start, win_idx, split_int=False, split_dist=False, center_weight=1.0, local_weight=1.0, centers=None,
@@ -954,16 +1064,15 @@ class PickPopulation(object):
                     keep.append(t)
                     tabs[kind * PICK_KEYS + key] = t.ctypes.data
                     sizes[kind * PICK_KEYS + key] = len(t)
-        check(lib().ia3_pick_scores_dev(self._h, _iptr(ws), _iptr(wi), 1 if split_int else 0, 1 if split_dist else 0,
-                                        C.c_double(float(center_weight)), C.c_double(float(local_weight)),
-                                        None if c is None else dptr(c), 1 if ref_is_picks else 0, tabs, _iptr(sizes),
-                                        1 if dist_only else 0))
+        check(lib().ia3_pick_scores_dev(self._h, ptr(ws), ptr(wi), 1 if split_int else 0, 1 if split_dist else 0,
+                                        float(center_weight), float(local_weight), None if c is None else ptr(c),
+                                        1 if ref_is_picks else 0, tabs, ptr(sizes), 1 if dist_only else 0))
 
     def difference(self):
         """(rows whose pick moved by less than 0.01, rows whose distance is not NaN) between the previous and the current
         picks: the 8-byte record of ``ia3_pick_difference_dev``."""
         out = np.zeros(2, dtype=np.int32)
-        check(lib().ia3_pick_difference_dev(self._h, _iptr(out)))
+        check(lib().ia3_pick_difference_dev(self._h, ptr(out)))
         return int(out[0]), int(out[1])
 
     def download(self, what):
@@ -982,25 +1091,11 @@ class PickPopulation(object):
         if n < 0:
             raise KeyError((kind, key))
         out = np.empty(n, dtype=np.float64)
-        check(lib().ia3_pick_download_sorted(self._h, int(kind), int(key), dptr(out)))
+        check(lib().ia3_pick_download_sorted(self._h, int(kind), int(key), ptr(out)))
         return out
 
-    def free(self):
-        if self._h is not None:
-            lib().ia3_pick_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.free()
+    def _release(self, handle):
+        lib().ia3_pick_free(handle)
 
 
 def poly_columns(order):
@@ -1023,9 +1118,8 @@ def poly_field(constants, orders, ref_center, shape, dtype=np.float64):
     od = np.array([int(o) for o in orders], dtype=np.int32)
     rc = np.ascontiguousarray(ref_center, dtype=np.float64)
     p = C.c_void_p()
-    check(lib().ia3_poly_field_dev(dptr(flat), ncol.ctypes.data_as(C.POINTER(C.c_int)), od.ctypes.data_as(C.POINTER(C.c_int)),
-                                   dptr(rc), int(shape[0]), int(shape[1]), int(shape[2]), 1 if dt == np.float32 else 2,
-                                   C.byref(p)))
+    check(lib().ia3_poly_field_dev(ptr(flat), ptr(ncol), ptr(od), ptr(rc), int(shape[0]), int(shape[1]), int(shape[2]),
+                                   1 if dt == np.float32 else 2, C.byref(p)))
     return p
 
 
@@ -1049,8 +1143,8 @@ def bleedthrough_profile(consts, present, order, ref_center, shape, mean_z=True,
     if len(ref_center) != 3 or len(shape) != 3:
         raise ValueError("a bleedthrough profile takes ref_center and shape of the three axes z, x, y")
     rc = np.ascontiguousarray(ref_center, dtype=np.float64)
-    p, ns = C.c_void_p(), C.c_longlong(0)
-    check(lib().ia3_bleedthrough_profile_dev(dptr(cs), pr.ctypes.data_as(C.POINTER(C.c_ubyte)), int(cs.shape[0]), order, dptr(rc),
+    p, ns = C.c_void_p(), C.c_int64(0)
+    check(lib().ia3_bleedthrough_profile_dev(ptr(cs), ptr(pr), int(cs.shape[0]), order, ptr(rc),
                                             int(shape[0]), int(shape[1]), int(shape[2]), 1 if mean_z else 0,
                                             1 if invert else 0, 1 if dt == np.float32 else 2, C.byref(p), C.byref(ns)))
     if ns.value > 0:
@@ -1110,11 +1204,11 @@ def make_seed_params(th_seed, gfilt_size=0.75, background_gfilt_size=7.5, filt_s
     if p.gfilt_size > 0:
         w, r = gaussian_taps(p.gfilt_size)
         keep.append(w)
-        p.w_front, p.r_front = dptr(w), r
+        p.w_front, p.r_front = ptr(w), r
     if p.background_gfilt_size > 0:
         w, r = gaussian_taps(p.background_gfilt_size)
         keep.append(w)
-        p.w_back, p.r_back = dptr(w), r
+        p.w_back, p.r_back = ptr(w), r
     return p, keep
 
 
@@ -1226,7 +1320,7 @@ def process_movies(params, movies, drifts_in=None, measure_drift=True, want_imag
 DIST_NANMEDIAN, DIST_NANMEAN, DIST_CONTACT = 0, 1, 2      # IA3_DIST_*
 
 
-class DistancePopulation(object):
+class DistancePopulation(Owner):
     """The (rows, 3) float64 coordinate tables of M chromosome copies resident in HBM (owner of an
     ``ia3_dist_population`` handle), and on it the summaries of structure_tools/distance.py over pairs of copies."""
 
@@ -1251,7 +1345,7 @@ class DistancePopulation(object):
         np.cumsum(rows, out=start[1:])
         packed = np.ascontiguousarray(np.concatenate(ts, axis=0)) if start[-1] > 0 else np.zeros((1, 3))
         h = C.c_void_p()
-        check(lib().ia3_dist_create(dptr(packed), _iptr(start), len(ts), C.byref(h)))
+        check(lib().ia3_dist_create(ptr(packed), ptr(start), len(ts), C.byref(h)))
         return cls(h, rows)
 
     def summary(self, pair_a, pair_b, function=DIST_NANMEDIAN, contact_th=None, same=False, return_counts=False):
@@ -1273,27 +1367,12 @@ class DistancePopulation(object):
         nf = np.empty((Ra, Rb), dtype=np.int32) if return_counts else None
         nc = np.empty((Ra, Rb), dtype=np.int32) if return_counts else None
         th = float("nan") if contact_th is None else float(contact_th)
-        check(lib().ia3_dist_summary_dev(self._h, _iptr(a), _iptr(b), len(a), Ra, Rb, 1 if same else 0, int(function),
-                                         C.c_double(th), dptr(out), None if nf is None else _iptr(nf),
-                                         None if nc is None else _iptr(nc)))
+        check(lib().ia3_dist_summary_dev(self._h, ptr(a), ptr(b), len(a), Ra, Rb, 1 if same else 0, int(function),
+                                         th, ptr(out), None if nf is None else ptr(nf), None if nc is None else ptr(nc)))
         return (out, nf, nc) if return_counts else out
 
-    def free(self):
-        if self._h is not None:
-            lib().ia3_dist_free(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
-
-    def __enter__(self):
-        return self
-
-    def __exit__(self, *a):
-        self.free()
+    def _release(self, handle):
+        lib().ia3_dist_free(handle)
 
 
 def dist_contact_stack(stack, contact_th, return_counts=False):
@@ -1304,6 +1383,5 @@ def dist_contact_stack(stack, contact_th, return_counts=False):
     N, K = v.shape[0], v.size // v.shape[0]
     prob = np.empty(v.shape[1:], dtype=np.float64)
     nf, nc = np.empty(v.shape[1:], dtype=np.int32), np.empty(v.shape[1:], dtype=np.int32)
-    check(lib().ia3_dist_contact_stack_dev(dptr(v), C.c_longlong(N), C.c_longlong(K), C.c_double(float(contact_th)), dptr(prob),
-                                           _iptr(nf), _iptr(nc)))
+    check(lib().ia3_dist_contact_stack_dev(ptr(v), N, K, float(contact_th), ptr(prob), ptr(nf), ptr(nc)))
     return (prob, nf, nc) if return_counts else prob

@@ -33,7 +33,7 @@ def _fftalign_2d(im1, im2, center, max_disp, convention, return_cor):
     out = (C.c_int * 2)()
     cor = C.c_double(0.)
     L.check(L.lib().ia3_fftalign_2d_ex(L.dptr(a), a.shape[0], a.shape[1], L.dptr(b), b.shape[0], b.shape[1],
-                                       L.dptr(c), C.c_double(float(max_disp)), int(convention), out,
+                                       L.dptr(c), float(max_disp), int(convention), out,
                                        C.byref(cor) if return_cor else None))
     return (int(out[0]), int(out[1]), float(cor.value)) if return_cor else (int(out[0]), int(out[1]))
 
@@ -47,7 +47,7 @@ def fftalign_2d(im1, im2, center=[0, 0], max_disp=150, plt_val=False):
     c = np.ascontiguousarray(center, dtype=np.float64)
     out = (C.c_int * 2)()
     L.check(L.lib().ia3_fftalign_2d(L.dptr(a), a.shape[0], a.shape[1], L.dptr(b), b.shape[0], b.shape[1],
-                                    L.dptr(c), C.c_double(float(max_disp)), out))
+                                    L.dptr(c), float(max_disp), out))
     return int(out[0]), int(out[1])
 
 
@@ -59,13 +59,13 @@ def _fft3d_from2d(im1, im2, gb, mode, convention, max_disp, return_cor):
     pc = cor if return_cor else None
     if isinstance(im1, L.DeviceStack) and isinstance(im2, L.DeviceStack):
         L.check(L.lib().ia3_fft3d_from2d_dev_ex(im1._h, im2._h, int(gb), int(mode), int(convention),
-                                                C.c_double(float(max_disp)), out, pc))
+                                                float(max_disp), out, pc))
     else:
         a, b = L.as_stack_array(_host(im1)), L.as_stack_array(_host(im2))
         if a.shape != b.shape or a.dtype != b.dtype:
             raise IndexError("fft3d_from2d needs two stacks of the same shape and dtype")
         L.check(L.lib().ia3_fft3d_from2d_ex(L.ptr(a), L.ptr(b), L.dtype_code(a), a.shape[0], a.shape[1], a.shape[2],
-                                            int(gb), int(mode), int(convention), C.c_double(float(max_disp)), out, pc))
+                                            int(gb), int(mode), int(convention), float(max_disp), out, pc))
     t = np.array([out[0], out[1], out[2]])
     return (t, float(cor[0]), float(cor[1])) if return_cor else t
 
@@ -77,13 +77,13 @@ def fft3d_from2d(im1, im2, gb=5, max_disp=150):
         return _fft3d_from2d(im1, im2, gb, L.BLUR_DIVIDE, L.OFFSET_ALIGNMENT_TOOLS, max_disp, False)
     out = (C.c_int * 3)()
     if isinstance(im1, L.DeviceStack) and isinstance(im2, L.DeviceStack):
-        L.check(L.lib().ia3_fft3d_from2d_dev(im1._h, im2._h, C.c_double(float(max_disp)), out))
+        L.check(L.lib().ia3_fft3d_from2d_dev(im1._h, im2._h, float(max_disp), out))
     else:
         a, b = L.as_stack_array(_host(im1)), L.as_stack_array(_host(im2))
         if a.shape != b.shape or a.dtype != b.dtype:
             raise IndexError("fft3d_from2d needs two stacks of the same shape and dtype")
         L.check(L.lib().ia3_fft3d_from2d(L.ptr(a), L.ptr(b), L.dtype_code(a), a.shape[0], a.shape[1], a.shape[2],
-                                         C.c_double(float(max_disp)), out))
+                                         float(max_disp), out))
     return np.array([out[0], out[1], out[2]])
 
 

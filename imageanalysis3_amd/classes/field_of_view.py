@@ -60,13 +60,11 @@ def _rounded_shifts(flags, drifts, shape):
 def _add_warped(chrom, stack, drift):
     """:1900-1901 — ``shift(im, -drift, order=1, mode='constant', cval=find_image_background(im))`` is
     ``map_coordinates(im, grid + drift, ...)`` in every byte: the order-1 constant warp, added as it is."""
-    import ctypes as C
     from ..io_tools.load import find_image_background
     cval = find_image_background(stack)
     minus = np.ascontiguousarray(-np.asarray(drift, dtype=np.float64))   # the warp reads at grid - drift
     with L.DeviceStack.empty(stack.shape, np.uint16) as shifted:
-        L.check(L.lib().ia3_warp3d_dev(stack._h, L.dptr(minus), None, 0, 1, L.MODE_CONSTANT, C.c_double(float(cval)),
-                                       shifted._h))
+        L.check(L.lib().ia3_warp3d_dev(stack._h, L.dptr(minus), None, 0, 1, L.MODE_CONSTANT, float(cval), shifted._h))
         chrom.add([shifted], [2], [[0, 0, 0]])
 
 

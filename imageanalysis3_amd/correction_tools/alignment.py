@@ -68,7 +68,7 @@ def phase_cross_correlation(reference_image, moving_image, upsample_factor=1, no
     return np.array([shift[0], shift[1], shift[2]]), float(err.value), float(ph.value)
 
 
-class DriftReference(object):
+class DriftReference(L.Owner):
     """The reference bead image of a run with the half spectra of its drift crops kept on the device
     (``ia3_drift_ref``): every image of a run is aligned to the same reference (classes/batch_functions.py:169-206), so
     its transforms are made once.  Hand it to ``align_image`` as ``ref_im``; drifts are those of the plain image.
@@ -88,22 +88,13 @@ class DriftReference(object):
         lims[:, :, 1] = np.minimum(lims[:, :, 1], np.array(self.shape)[None, :])
         self.crops = np.ascontiguousarray(lims, dtype=np.int32)
         h = C.c_void_p()
-        L.check(L.lib().ia3_drift_ref_create(self.stack._h, self.crops.ctypes.data_as(C.POINTER(C.c_int)), len(self.crops),
-                                             C.byref(h)))
+        L.check(L.lib().ia3_drift_ref_create(self.stack._h, L.ptr(self.crops), len(self.crops), C.byref(h)))
         self._h = h
 
-    def free(self):
-        if getattr(self, "_h", None) is not None:
-            L.lib().ia3_drift_ref_free(self._h)
-            self._h = None
-            if self._own:
-                self.stack.free()
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self, handle):
+        L.lib().ia3_drift_ref_free(handle)
+        if self._own:
+            self.stack.free()
 
 
 def align_beads(tar_cts, ref_cts,
@@ -269,12 +260,12 @@ def align_image(
             if _dref is not None:
                 L.check(L.lib().ia3_align_image_ref(_src._h, _dref._h, int(precision_fold),
                                                     1 if DEFAULT_NORMALIZATION == "phase" else 0, int(min_good_drifts),
-                                                    C.c_double(float(drift_diff_th)), _out, C.byref(_flag), L.dptr(_each),
+                                                    float(drift_diff_th), _out, C.byref(_flag), L.dptr(_each),
                                                     C.byref(_nused)))
             else:
-                L.check(L.lib().ia3_align_image_dev(_src._h, _ref._h, _cl.ctypes.data_as(C.POINTER(C.c_int)), len(_cl),
+                L.check(L.lib().ia3_align_image_dev(_src._h, _ref._h, L.ptr(_cl), len(_cl),
                                                     int(precision_fold), 1 if DEFAULT_NORMALIZATION == "phase" else 0,
-                                                    int(min_good_drifts), C.c_double(float(drift_diff_th)), _out,
+                                                    int(min_good_drifts), float(drift_diff_th), _out,
                                                     C.byref(_flag), L.dptr(_each), C.byref(_nused)))
             _drifts = [_each[_i].copy() for _i in range(_nused.value)]
             if verbose:

@@ -13,7 +13,7 @@ def gaussian_filter(image, sigma, mode='reflect', truncate=4.0):
     out = np.empty_like(a)
     m = {'reflect': L.MODE_REFLECT, 'nearest': L.MODE_NEAREST}[mode]
     L.check(L.lib().ia3_gaussian_filter(L.ptr(a), L.dtype_code(a), a.shape[0], a.shape[1], a.shape[2],
-                                        C.c_double(sigma), C.c_double(truncate), m, L.dptr(w), r, L.ptr(out)))
+                                        sigma, truncate, m, L.dptr(w), r, L.ptr(out)))
     return out
 
 
@@ -31,7 +31,7 @@ def gaussian_high_pass_filter(image, sigma=5, truncate=2):
     w, r = L.gaussian_taps(sigma, truncate)
     out = np.empty_like(a)
     L.check(L.lib().ia3_gaussian_highpass(L.ptr(a), L.dtype_code(a), a.shape[0], a.shape[1], a.shape[2],
-                                          C.c_double(sigma), C.c_double(truncate), L.dptr(w), r, L.ptr(out)))
+                                          sigma, truncate, L.dptr(w), r, L.ptr(out)))
     return out
 
 
@@ -44,7 +44,7 @@ def Remove_Hot_Pixels(im, dtype=np.uint16, hot_pix_th=0.50, hot_th=4,
     out = np.empty_like(a)
     n_hot = C.c_int(0)
     L.check(L.lib().ia3_remove_hot_pixels(L.ptr(a), L.dtype_code(a), a.shape[0], a.shape[1], a.shape[2],
-                                          C.c_double(hot_pix_th), C.c_double(hot_th), L.ptr(out), C.byref(n_hot)))
+                                          hot_pix_th, hot_th, L.ptr(out), C.byref(n_hot)))
     if n_hot.value == 0:
         return im                                                            # :32-33
     if interpolation_style != 'nearest':

@@ -5,7 +5,6 @@ device on the stacks ``correct_fov_image(..., return_device=True)`` leaves resid
 csrc/stats.hip); results equal the reference's bit for bit.  All ``file:line`` citations are relative to the reference
 tree.
 """
-import ctypes as C
 import os
 import time
 import numpy as np
@@ -29,8 +28,8 @@ def _stack_to_profile(stack, remove_cap=True, cap_th_per=[5, 90], gaussian_filte
         _out = np.empty(tuple(_st.shape[1:]), dtype=np.float64)
         _wp, _r, _keep = L.taps_argument(gaussian_filter_size)
         L.check(L.lib().ia3_illumination_image_profile_dev(
-            _st._h, 1 if remove_cap else 0, C.c_double(float(min(cap_th_per))), C.c_double(float(max(cap_th_per))),
-            C.c_double(float(gaussian_filter_size)), _wp, _r, L.dptr(_out)))
+            _st._h, 1 if remove_cap else 0, float(min(cap_th_per)), float(max(cap_th_per)),
+            float(gaussian_filter_size), _wp, _r, L.dptr(_out)))
     finally:
         if not _resident:
             _st.free()

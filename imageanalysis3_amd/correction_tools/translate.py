@@ -1,5 +1,4 @@
 """Drop-in for the reference's ``correction_tools/translate.py`` (warp.hip)."""
-import ctypes as C
 import time
 import numpy as np
 
@@ -30,7 +29,7 @@ def warp_3d_image(image, drift, chromatic_profile=None,
             raise IndexError(f"chromatic_profile shape {tuple(chromatic_profile.shape)} should be {(3,) + a.shape}")
         with L.DeviceStack.upload(a) as _src, L.DeviceStack.empty(a.shape, a.dtype) as _dst:
             L.check(L.lib().ia3_warp3d_dev(_src._h, L.dptr(_drift), chromatic_profile.ptr, chromatic_profile.dtype_code,
-                                           int(warp_order), _MODES[border_mode], C.c_double(float(np.min(a))), _dst._h))
+                                           int(warp_order), _MODES[border_mode], float(np.min(a)), _dst._h))
             out = _dst.download()
         if verbose:
             print(f"-- finish warp image in {time.time()-_start_time:.3f}s. ")
@@ -46,7 +45,7 @@ def warp_3d_image(image, drift, chromatic_profile=None,
     out = np.empty_like(a)
     L.check(L.lib().ia3_warp3d(L.ptr(a), L.dtype_code(a), a.shape[0], a.shape[1], a.shape[2], L.dptr(_drift),
                                L.ptr(field) if field is not None else None, fdt, int(warp_order),
-                               _MODES[border_mode], C.c_double(float(np.min(a))), L.ptr(out)))
+                               _MODES[border_mode], float(np.min(a)), L.ptr(out)))
     if verbose:
         print(f"-- finish warp image in {time.time()-_start_time:.3f}s. ")
     return out

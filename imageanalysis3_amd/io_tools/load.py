@@ -271,9 +271,10 @@ def split_im_by_channels(im, sel_channels, all_channels, single_im_size=None,
     return [im[_s:_s + Z * _n:_n].copy() for _s in starts]
 
 
-class DeviceBuffer(object):
+class DeviceBuffer(L.Owner):
     """A run-constant array (correction profile) resident in HBM: uploaded from ``arr``, or made on the device
     (``DeviceBuffer.empty`` / ``DeviceBuffer.adopt``; ``arr`` is then None).  ``shape`` and ``dtype`` describe it either way."""
+    _handle = "ptr"
 
     def __init__(self, arr):
         self.arr = np.ascontiguousarray(arr)
@@ -283,7 +284,7 @@ class DeviceBuffer(object):
             self.dtype_code = 2
         self.shape, self.dtype = tuple(self.arr.shape), self.arr.dtype
         p = C.c_void_p()
-        L.check(L.lib().ia3_buffer_upload(L.ptr(self.arr), C.c_size_t(self.arr.nbytes), C.byref(p)))
+        L.check(L.lib().ia3_buffer_upload(L.ptr(self.arr), self.arr.nbytes, C.byref(p)))
         self.ptr = p
 
     @classmethod
@@ -306,25 +307,17 @@ class DeviceBuffer(object):
         if dt not in (np.dtype(np.float32), np.dtype(np.float64)):
             raise TypeError("a device buffer is float32 or float64, got %s" % dt)
         p = C.c_void_p()
-        L.check(L.lib().ia3_buffer_alloc(C.c_size_t(int(np.prod(shape)) * dt.itemsize), C.byref(p)))
+        L.check(L.lib().ia3_buffer_alloc(int(np.prod(shape)) * dt.itemsize, C.byref(p)))
         return cls.adopt(p, shape, dt)
 
     def download(self):
         """The buffer's contents as a new ndarray of ``shape`` and ``dtype``."""
         out = np.empty(self.shape, dtype=self.dtype)
-        L.check(L.lib().ia3_buffer_download(self.ptr, C.c_size_t(out.nbytes), L.ptr(out)))
+        L.check(L.lib().ia3_buffer_download(self.ptr, out.nbytes, L.ptr(out)))
         return out
 
-    def free(self):
-        if self.ptr is not None:
-            L.lib().ia3_buffer_free(self.ptr)
-            self.ptr = None
-
-    def __del__(self):
-        try:
-            self.free()
-        except Exception:
-            pass
+    def _release(self, handle):
+        L.lib().ia3_buffer_free(handle)
 
 
 def _as_buffer(p):
@@ -467,8 +460,7 @@ def correct_fov_image(dax_filename, sel_channels,
         if hot_pixel_corr:                                                   # :323-334
             for _im in _ims:
                 nh = C.c_int(0)
-                L.check(lib.ia3_remove_hot_pixels_dev(_im._h, C.c_double(0.5), C.c_double(float(hot_pixel_th)), 1,
-                                                      C.byref(nh)))
+                L.check(lib.ia3_remove_hot_pixels_dev(_im._h, 0.5, float(hot_pixel_th), 1, C.byref(nh)))
         if z_shift_corr:                                                     # :337-345
             for _im in _ims:
                 L.check(lib.ia3_z_shift_correction_dev(_im._h, _im._h))
@@ -530,14 +522,14 @@ def correct_fov_image(dax_filename, sel_channels,
                 _out = L.DeviceStack.empty(_ims[_i].shape, np.uint16)
                 _owned.append(_out)
                 L.check(lib.ia3_warp3d_dev(_ims[_i]._h, L.dptr(_d), _field, _fdt, 3, L.MODE_NEAREST,
-                                           C.c_double(0.0), _out._h))
+                                           0.0, _out._h))
                 _ims[_i] = _out
         if gaussian_highpass:                                                # :489-498 (every loaded channel)
             w, r = L.gaussian_taps(gauss_sigma, gauss_truncate)
             for _i, _im in enumerate(_ims):
                 _out = L.DeviceStack.empty(_im.shape, np.uint16)
                 _owned.append(_out)
-                L.check(lib.ia3_gaussian_highpass_dev(_im._h, C.c_double(gauss_sigma), C.c_double(gauss_truncate),
+                L.check(lib.ia3_gaussian_highpass_dev(_im._h, gauss_sigma, gauss_truncate,
                                                       L.dptr(w), int(r), _out._h))
                 _ims[_i] = _out
         _sel = [_ims[_load_channels.index(_ch)] for _ch in sel_channels]

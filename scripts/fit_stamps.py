@@ -29,7 +29,7 @@ for waves in (1, 2):
         L.check(lib.ia3_fit_create(st._h, L.dptr(seeds), len(seeds), C.byref(fp), C.byref(hh)))
         L.check(lib.ia3_fit_run(hh))
         cnt = np.zeros(32, np.uint64)
-        L.check(lib.ia3_fit_counters(hh, cnt.ctypes.data_as(C.c_void_p)))
+        L.check(lib.ia3_fit_counters(hh, L.ptr(cnt)))
         lib.ia3_fit_destroy(hh)
     tot = float(cnt[8:].sum() - cnt[8 + 15] - cnt[8 + 16])
     nw = 4 * 256 * waves

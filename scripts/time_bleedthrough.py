@@ -12,6 +12,7 @@ and its NumPy restatement.
      256 x 256 tile on this machine's CPU, scaled by area to the full size and labelled as scaled.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -67,13 +68,13 @@ def main():
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "bleedthrough.json"))
     a = ap.parse_args()
     L.check(L.lib().ia3_init(0))
-    name = np.zeros(256, dtype=np.uint8)
-    L.lib().ia3_device_name(L.ptr(name), 256)
+    name = C.create_string_buffer(256)
+    L.lib().ia3_device_name(name, 256)
     order, n_ch = 2, 3
     consts, present = B.tail_constants(n_ch, order, 1)
     consts = consts * (50.0 / (a.size / 2)) ** 2          # the polynomials stay below 0.3 over the larger field
     res = dict(size=a.size, runs=a.runs, channels=n_ch, fitting_order=order, dtype="float64",
-               gpu=bytes(name).split(b"\0")[0].decode(), kernel={})
+               gpu=name.value.decode(), kernel={})
 
     def write():
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)

@@ -11,6 +11,7 @@
       whether it equals the device's sum of those.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -43,9 +44,9 @@ def main():
     shape, K = tuple(a.shape), a.images
     nvox = int(np.prod(shape))
     L.check(L.lib().ia3_init(0))
-    name = np.zeros(256, dtype=np.uint8)
-    L.lib().ia3_device_name(L.ptr(name), 256)
-    res = dict(shape=list(shape), images=K, runs=a.runs, gpu=bytes(name).split(b"\0")[0].decode())
+    name = C.create_string_buffer(256)
+    L.lib().ia3_device_name(name, 256)
+    res = dict(shape=list(shape), images=K, runs=a.runs, gpu=name.value.decode())
     base = synthetic(shape, "u16")
     rng = np.random.RandomState(3)
     drifts = np.round(rng.uniform(-6, 6, size=(K, 3)) * np.array([0.3, 1, 1]), 2).astype(np.float32)

@@ -11,6 +11,7 @@
       the pair count; generate_polynomial_data and np.dot for one axis of the field, as the reference computes it).
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -61,9 +62,9 @@ def main():
     a = ap.parse_args()
     shape = tuple(a.shape)
     L.check(L.lib().ia3_init(0))
-    name = np.zeros(256, dtype=np.uint8)
-    L.lib().ia3_device_name(L.ptr(name), 256)
-    res = dict(shape=list(shape), pairs=a.pairs, runs=a.runs, gpu=bytes(name).split(b"\0")[0].decode())
+    name = C.create_string_buffer(256)
+    L.lib().ia3_device_name(name, 256)
+    res = dict(shape=list(shape), pairs=a.pairs, runs=a.runs, gpu=name.value.decode())
 
     # (i) boxes and regressions: the stacks need not be large, the kernel reads 11^3 voxels per box
     cshape = (30, 512, 512)

@@ -10,6 +10,7 @@
 (iii) the host statement of the same chain (tests/harness/chromseg_ref.py) on a smaller stack, one run.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -73,10 +74,10 @@ def main():
     a = ap.parse_args()
     shape = tuple(a.shape)
     L.check(L.lib().ia3_init(0))
-    name = np.zeros(256, dtype=np.uint8)
-    L.lib().ia3_device_name(L.ptr(name), 256)
+    name = C.create_string_buffer(256)
+    L.lib().ia3_device_name(name, 256)
     res = dict(shape=list(shape), dtype=a.dtype, runs=a.runs, filt_size=a.filt_size, per=a.per, min_size=a.min_size,
-               gpu=bytes(name).split(b"\0")[0].decode())
+               gpu=name.value.decode())
     im = synthetic(shape, a.dtype)
 
     def wall(fn):

@@ -20,6 +20,7 @@ expressions, on one core for the first regions / sqrt(`--fraction`) regions of t
 of its distances.  Both parts write into the same JSON file.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -100,9 +101,9 @@ def main():
     from imageanalysis3_amd import _lib as L
     from imageanalysis3_amd.structure_tools import distance as D
     L.check(L.lib().ia3_init(0))
-    name = np.zeros(256, dtype=np.uint8)
-    L.lib().ia3_device_name(L.ptr(name), 256)
-    gpu = bytes(name).split(b"\0")[0].decode()
+    name = C.create_string_buffer(256)
+    L.lib().ia3_device_name(name, 256)
+    gpu = name.value.decode()
     # ---- one cis key
     t = walks(N, R, 3)
     t0 = time.perf_counter()

@@ -10,6 +10,7 @@
       the stack, two np.partition percentiles on the host, seed from the host copy (a second upload), fit.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -60,9 +61,9 @@ def main():
     a = ap.parse_args()
     shape = tuple(a.shape)
     L.check(L.lib().ia3_init(0))
-    name = np.zeros(256, dtype=np.uint8)
-    L.lib().ia3_device_name(L.ptr(name), 256)
-    res = dict(shape=list(shape), runs=a.runs, gpu=bytes(name).split(b"\0")[0].decode())
+    name = C.create_string_buffer(256)
+    L.lib().ia3_device_name(name, 256)
+    res = dict(shape=list(shape), runs=a.runs, gpu=name.value.decode())
 
     f32 = synth.make_fov(shape, a.spots, 7)[0]
     x, y = np.meshgrid(np.arange(shape[1]), np.arange(shape[2]), indexing="ij")

@@ -18,6 +18,7 @@ With --cpu-statement (no GPU): the statement, which is the reference's arithmeti
 of the chromosomes on one CPU core.  Both parts write into the same JSON file.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -102,8 +103,8 @@ def main():
     from imageanalysis3_amd import _lib as L
     from imageanalysis3_amd.spot_tools import picking as PK
     L.check(L.lib().ia3_init(0))
-    name = np.zeros(256, dtype=np.uint8)
-    L.lib().ia3_device_name(L.ptr(name), 256)
+    name = C.create_string_buffer(256)
+    L.lib().ia3_device_name(name, 256)
     cands, channels = workload(P, R)
     t0 = time.perf_counter()
     packed = PK._pack(cands)
@@ -131,7 +132,7 @@ def main():
     lens = pop.lengths.copy()
     log_bytes = int(sum(8 * len(t) for _, t in pop._logs.values()))
     ws, wi = PK._windows(pop.cand_ids, pop.ref_ids, NEIGHBOR_LEN, pop.ref_channels, True)
-    out = dict(shape, gpu=bytes(name).split(b"\0")[0].decode(), runs=a.runs, candidates=int(pop.n),
+    out = dict(shape, gpu=name.value.decode(), runs=a.runs, candidates=int(pop.n),
                host_pack_ms=pack_ms, upload_ms=upload_ms, upload_bytes=int(packed[0].nbytes + packed[1].nbytes + packed[2].nbytes),
                stage_ms_over_all_iterations=med, stage_sum_ms=float(sum(med.values())),
                loop_wall_ms=float(np.median(walls)), ratios=[float(r) for r in ratios],

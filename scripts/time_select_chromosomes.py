@@ -18,6 +18,7 @@ algorithm, on the same input on this host's CPU; it runs for minutes (--max-pass
 parts write into the same JSON file.
 """
 import argparse
+import ctypes as C
 import json
 import os
 import sys
@@ -89,8 +90,8 @@ def main():
     from imageanalysis3_amd import _distance_zxy, _lib as L
     from imageanalysis3_amd.segmentation_tools import chromosome as CH
     L.check(L.lib().ia3_init(0))
-    name = np.zeros(256, dtype=np.uint8)
-    L.lib().ia3_device_name(L.ptr(name), 256)
+    name = C.create_string_buffer(256)
+    L.lib().ia3_device_name(name, 256)
     t0 = time.perf_counter()
     _, zxys, starts = CH._pack_rounds(spots_list, 0.5, _distance_zxy)
     chrom = np.array(list(cands)) * np.array(_distance_zxy)
@@ -108,7 +109,7 @@ def main():
     up, first, loop = np.median(np.array(parts), axis=0)
     n_rem = int(len(res["removed"]))
     S, C = len(zxys), len(chrom)
-    out = dict(shape, gpu=bytes(name).split(b"\0")[0].decode(), runs=a.runs, selected_spots=S, upload_ms=float(up),
+    out = dict(shape, gpu=name.value.decode(), runs=a.runs, selected_spots=S, upload_ms=float(up),
                upload_bytes=int(zxys.nbytes + chrom.nbytes + starts.nbytes), first_pass_ms=float(first),
                first_pass_distances=S * C, removal_loop_ms=float(loop), removals=n_rem, kept=int(len(kept)),
                removal_mean_ms=float(loop / n_rem) if n_rem else None, library_call_wall_ms=float(np.median(walls)),

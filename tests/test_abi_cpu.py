@@ -8,20 +8,153 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _declared():
+def _header():
     src = open(os.path.join(ROOT, "include", "ia3.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(ia3_[a-z0-9_]+)\s*\(", src)))
+    return re.sub(r"/\*.*?\*/", "", src, flags=re.S)
 
 
-def test_header_symbols_exported():
+def _ctype(decl, _lib):
+    """The ctypes type of a C type by the rule stated above ``_lib.PROTOTYPES``."""
+    scalars = {"int": C.c_int, "double": C.c_double, "long long": C.c_longlong, "size_t": C.c_size_t, "float": C.c_float,
+               "uint8_t": C.c_ubyte, "unsigned char": C.c_ubyte, "int64_t": C.c_int64, "uint64_t": C.c_uint64}
+    structs = {"ia3_seed_params": _lib.SeedParams, "ia3_fit_params": _lib.FitParams,
+               "ia3_legacy_seed_params": _lib.LegacySeedParams, "ia3_chrom_params": _lib.ChromParams,
+               "ia3_movie_params": _lib.MovieParams, "ia3_movie_job": _lib.MovieJob, "ia3_fov_job": _lib.FovJob}
+    handles = {"ia3_stack", "ia3_fitter", "ia3_chrom_image", "ia3_pick_population", "ia3_dist_population", "ia3_drift_ref"}
+    base = " ".join(re.sub(r"\bconst\b", " ", decl.replace("*", " ")).split())
+    stars = decl.count("*")
+    if stars == 0:
+        return None if base == "void" else scalars[base]
+    if stars > 1 or base == "void" or base in handles:
+        return C.c_void_p
+    if base == "char":
+        return C.c_char_p
+    if base in structs:
+        return C.POINTER(structs[base])
+    return C.POINTER(C.c_int64 if base == "long long" else scalars[base])
+
+
+def _declared(_lib):
+    """name -> (restype, [argtypes]) of every function include/ia3.h declares."""
+    found = {}
+    for res, name, args in re.findall(r"(?m)^((?:const\s+)?(?:int|void|char)\s*\*?)\s*(ia3_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", _header()):
+        assert name not in found, name
+        params = [] if args.strip() == "void" else [re.sub(r"\s*\b[A-Za-z_][A-Za-z_0-9]*\s*$", "", a.strip()) for a in args.split(",")]
+        found[name] = (_ctype(res, _lib), [_ctype(p, _lib) for p in params])
+    return found
+
+
+def test_header_equals_the_prototype_table():
+    import subprocess
+    from imageanalysis3_amd import _lib
+    lib, found = _lib.lib(), _declared(_lib)
+    nm = subprocess.check_output(["nm", "-D", "--defined-only", _lib.LIB_PATH]).decode()
+    exported = sorted(n for n in re.findall(r"\bT (ia3_[a-z0-9_]+)$", nm, flags=re.M))
+    assert sorted(found) == exported and len(exported) >= 137
+    assert sorted(found) == sorted(_lib.PROTOTYPES) and _lib.EXPORTS == list(_lib.PROTOTYPES)
+    assert C.sizeof(C.c_int64) == C.sizeof(C.c_longlong) and np.ctypeslib.as_ctypes_type(np.int64) is C.c_int64
+    for name, (res, types) in found.items():
+        assert _lib.PROTOTYPES[name][0] is res and list(_lib.PROTOTYPES[name][1]) == types, name
+        fn = getattr(lib, name)
+        assert fn.restype is res and list(fn.argtypes) == types, name
+
+
+def test_every_call_site_has_the_declared_arity():
+    """Every call of an attribute named like an entry, anywhere in the repository's Python, passes as many positional
+    arguments as the header declares and no keywords, and none hands ``ptr(array)`` to a ``char*`` parameter.  A call with a
+    starred argument cannot be counted; there are two."""
+    import ast
+    import glob
+    from imageanalysis3_amd import _lib
+    files = [os.path.join(ROOT, "bench.py"), os.path.join(ROOT, "__graft_entry__.py")]
+    for d in ("imageanalysis3_amd", "tests", "scripts"):
+        files += glob.glob(os.path.join(ROOT, d, "**", "*.py"), recursive=True)
+    counted, starred, wrong = 0, [], []
+    for path in sorted(files):
+        for node in ast.walk(ast.parse(open(path).read(), path)):
+            if not (isinstance(node, ast.Call) and isinstance(node.func, ast.Attribute) and node.func.attr in _lib.PROTOTYPES):
+                continue
+            where = "%s:%d %s" % (os.path.relpath(path, ROOT), node.lineno, node.func.attr)
+            if any(isinstance(a, ast.Starred) for a in node.args):
+                starred.append(where)
+            elif len(node.args) != len(_lib.PROTOTYPES[node.func.attr][1]) or node.keywords:
+                wrong.append(where)
+            else:
+                counted += 1
+                # ptr() of an array is never a char*: such a parameter takes bytes or a ctypes string buffer
+                for arg, t in zip(node.args, _lib.PROTOTYPES[node.func.attr][1]):
+                    f = arg.func if isinstance(arg, ast.Call) else None
+                    if t is C.c_char_p and getattr(f, "attr", getattr(f, "id", None)) in ("ptr", "dptr", "_iptr"):
+                        wrong.append(where + " (ptr() for a char*)")
+    assert not wrong, wrong
+    assert [w.split(":")[0] + " " + w.split()[1] for w in starred] == [
+        "imageanalysis3_amd/External/Fitting_v4.py ia3_fastfit_moments_dev", "imageanalysis3_amd/_lib.py ia3_crop_pairs_dev"], starred
+    assert counted >= 449
+
+
+def test_mistakes_are_refused_before_c_is_entered():
     from imageanalysis3_amd import _lib
     lib = _lib.lib()
-    names = _declared()
-    assert len(names) >= 25
-    missing = [n for n in names if not hasattr(lib, n)]
-    assert not missing, missing
-    assert sorted(set(_lib.EXPORTS)) == names, (set(names) ^ set(_lib.EXPORTS))
+    a32, a64 = np.zeros((4, 4), dtype=np.float32), np.zeros((4, 4), dtype=np.float64)
+    with pytest.raises(C.ArgumentError):
+        lib.ia3_gaussian_filter2d_f64(_lib.ptr(a32), 4, 4, 1.0, 4.0, 0, None, 0, _lib.ptr(a64))
+    with pytest.raises(C.ArgumentError):
+        lib.ia3_set_tuning(1.5, 0)
+    with pytest.raises(C.ArgumentError):
+        lib.ia3_gaussian_filter2d_f64(C.c_void_p(a64.ctypes.data), 4, 4, 1.0, 4.0, 0, None, 0, _lib.ptr(a64))
+    # a Python int where a double is declared is converted: the call reaches C, which refuses the empty image (with a
+    # device) or finds no device
+    assert lib.ia3_gaussian_filter2d_f64(_lib.ptr(a64), 0, 0, 1, 4, 0, None, 0, _lib.ptr(a64)) in (_lib.IA3_EINVAL, _lib.IA3_EHIP)
+    assert _lib.ptr(a64)._type_ is C.c_double and _lib.ptr(a32)._type_ is C.c_float and _lib.dptr is _lib.ptr and _lib._iptr is _lib.ptr
+    assert _lib.ptr(np.zeros(2, np.int64))._type_ is C.c_int64 and _lib.ptr(np.zeros(2, np.uint8))._type_ is C.c_ubyte
+
+
+def test_constants_are_the_headers():
+    from imageanalysis3_amd import _lib
+    defines = {n: int(v.strip("()")) for n, v in re.findall(r"#define\s+(IA3_[A-Z0-9_]+)\s+(\(?-?\d+\)?)\s*$", _header(), flags=re.M)}
+    assert len(defines) >= 45
+    mirrored = [n for n in defines if hasattr(_lib, n)]
+    assert all(getattr(_lib, n) == defines[n] for n in mirrored), [n for n in mirrored if getattr(_lib, n) != defines[n]]
+    knobs = [n for n in defines if n.startswith(("IA3_TUNE_", "IA3_DEBUG_"))]
+    assert len(knobs) >= 21 and all(n in mirrored for n in knobs), set(knobs) - set(mirrored)
+    for n in ("IA3_U16", "IA3_F32", "IA3_OK", "IA3_EINVAL", "IA3_EHIP", "IA3_ENOMEM", "IA3_ECAPACITY", "IA3_EUNSUPPORTED",
+              "IA3_MODE_REFLECT", "IA3_MODE_NEAREST", "IA3_MODE_CONSTANT", "IA3_SELECT_THREADS", "IA3_SELECT_TILE",
+              "IA3_SELECT_EMPTY", "IA3_PICK_MAX_CHANNELS", "IA3_BLUR_MAX_GB", "IA3_BLUR_DIVIDE", "IA3_BLUR_SUBTRACT"):
+        assert n in mirrored, n
+
+
+def test_owner_releases_once():
+    from imageanalysis3_amd import _lib
+    released = []
+
+    class Fake(_lib.Owner):
+        def __init__(self, handle, fail=False):
+            if fail:
+                raise ValueError("before the handle exists")
+            self._h, self._keep = handle, object()
+
+        def _release(self, handle):
+            released.append(handle)
+
+    f = Fake(7)
+    f.free()
+    f.free()
+    assert released == [7] and f._h is None and f._keep is None
+    with Fake(8) as g:
+        assert g._h == 8
+    assert released == [7, 8] and g._h is None
+    broken = Fake.__new__(Fake)
+    with pytest.raises(ValueError):
+        broken.__init__(9, fail=True)
+    broken.__del__()
+    assert released == [7, 8]
+    Fake(10).__del__()
+    assert released == [7, 8, 10]
+    for cls in (_lib.DeviceStack, _lib.DeviceLabels, _lib.ChromImage, _lib.PickPopulation, _lib.DistancePopulation):
+        assert issubclass(cls, _lib.Owner) and "free" not in vars(cls) and "__del__" not in vars(cls)
+    from imageanalysis3_amd.io_tools.load import DeviceBuffer
+    from imageanalysis3_amd.correction_tools.alignment import DriftReference
+    assert issubclass(DeviceBuffer, _lib.Owner) and issubclass(DriftReference, _lib.Owner)
 
 
 def test_struct_layout_matches_header(tmp_path):
@@ -30,7 +163,8 @@ def test_struct_layout_matches_header(tmp_path):
     from imageanalysis3_amd import _lib
     pairs = [("ia3_seed_params", _lib.SeedParams), ("ia3_fit_params", _lib.FitParams),
              ("ia3_legacy_seed_params", _lib.LegacySeedParams), ("ia3_fov_job", _lib.FovJob),
-             ("ia3_movie_params", _lib.MovieParams), ("ia3_movie_job", _lib.MovieJob)]
+             ("ia3_movie_params", _lib.MovieParams), ("ia3_movie_job", _lib.MovieJob),
+             ("ia3_chrom_params", _lib.ChromParams)]
     lines = []
     for cname, ct in pairs:
         lines.append('printf("%s %%zu", sizeof(%s));' % (cname, cname))

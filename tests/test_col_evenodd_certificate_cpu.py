@@ -10,7 +10,6 @@ weights from the library's own builder) and checks the two statements the kernel
 (b) every output whose float32 rounding / uint16 truncation differs between the even/odd sum and NI_Correlate1D's own
     sequence is caught by "lopsided pair, or within the guard of a quantisation boundary", with the library's constants.
 """
-import ctypes as C
 import math
 import os
 import re
@@ -29,10 +28,7 @@ MODES = {"reflect": 0, "nearest": 1}
 
 def _lib():
     from imageanalysis3_amd import _lib as L
-    lib = L.lib()
-    lib.ia3_col_guard.argtypes = [C.c_int, C.c_int, C.c_int]
-    lib.ia3_col_weights.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_int]
-    return L, lib
+    return L, L.lib()
 
 
 def _taps():
@@ -157,16 +153,16 @@ KINDS = ("background_noise_f32", "poisson_u16", "half_zero_f32", "half_zero_mirr
 
 def test_weight_stream_and_guard_are_the_library_s():
     """The restated W / Wp / Wm stream equals ia3_col_weights bit for bit, and the default guard is the derived one."""
-    _, lib = _lib()
+    L, lib = _lib()
     w = _taps()
     K = _lopsided_k()
     for Z in (16, 25, 33, 50, 60, 64):
         for mode, code in MODES.items():
             stream = _weights(Z, mode, w)[3]
-            n = lib.ia3_col_weights(Z, R, code, w.ctypes.data, None, 0)
+            n = lib.ia3_col_weights(Z, R, code, L.ptr(w), None, 0)
             assert n == (len(stream) + 15) // 16 * 16 and len(stream) == (Z // 2) * Z + (Z & 1) * ((Z + 1) // 2)
             got = np.full(n, np.nan)
-            assert lib.ia3_col_weights(Z, R, code, w.ctypes.data, got.ctypes.data, n) == n
+            assert lib.ia3_col_weights(Z, R, code, L.ptr(w), L.ptr(got), n) == n
             assert np.array_equal(got[:len(stream)].view(np.uint64), stream.view(np.uint64)), (Z, mode)
             assert not got[len(stream):].any()
             nterms = (Z + 1) // 2

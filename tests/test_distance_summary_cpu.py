@@ -2,7 +2,6 @@
 outputs (tests/golden/distsum.npz), the reference's names and signatures, the ctypes mirrors against include/ia3.h, the
 argument errors that come before any device call, the plotting-order helpers against the reference's outputs, and the
 stand-alone check of csrc/ia3_distsum.h (tests/native/distsum_cpu.cpp), also under AddressSanitizer and UBSan."""
-import ctypes as C
 import functools
 import inspect
 import os
@@ -72,27 +71,12 @@ def test_names_and_signatures_are_the_references(D):
         "(zxys_a, zxys_b=None, function='nanmedian', contact_th=None, return_counts=False)"
 
 
-_CTYPES = {"int": C.c_int, "double": C.c_double, "long long": C.c_longlong, "const double*": C.POINTER(C.c_double),
-           "double*": C.POINTER(C.c_double), "const int*": C.POINTER(C.c_int), "int*": C.POINTER(C.c_int),
-           "ia3_dist_population*": C.c_void_p, "ia3_dist_population**": C.POINTER(C.c_void_p), "void": None}
-
-
 def test_ctypes_mirrors_match_the_header():
     from imageanalysis3_amd import _lib
     src = open(os.path.join(ROOT, "include", "ia3.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    found = {}
-    for res, name, args in re.findall(r"\b(int|void)\s+(ia3_dist_[a-z_]+)\s*\(([^)]*)\)\s*;", src):
-        types = []
-        for arg in args.split(","):
-            t = re.sub(r"\s*\b[A-Za-z_][A-Za-z_0-9]*\s*$", "", arg.strip())      # drop the parameter's name
-            types.append(_CTYPES[re.sub(r"\s*\*", "*", t)])
-        found[name] = (_CTYPES[res], types)
-    assert sorted(found) == sorted(_lib.DIST_PROTOTYPES) == sorted(e for e in _lib.EXPORTS if e.startswith("ia3_dist_"))
-    for name, (res, types) in found.items():
-        assert _lib.DIST_PROTOTYPES[name][0] is res and _lib.DIST_PROTOTYPES[name][1] == types, name
-        fn = getattr(_lib.lib(), name)
-        assert fn.restype is res and list(fn.argtypes) == types
+    found = re.findall(r"\b(?:int|void)\s+(ia3_dist_[a-z_]+)\s*\(", src)       # their prototypes: test_abi_cpu.py
+    assert sorted(found) == sorted(e for e in _lib.EXPORTS if e.startswith("ia3_dist_")) and len(found) == 4
     enum = re.search(r"enum\s*\{\s*IA3_DIST_NANMEDIAN = (\d+), IA3_DIST_NANMEAN = (\d+), IA3_DIST_CONTACT = (\d+)\s*\}", src)
     assert [int(v) for v in enum.groups()] == [_lib.DIST_NANMEDIAN, _lib.DIST_NANMEAN, _lib.DIST_CONTACT]
     assert int(re.search(r"#define IA3_TUNE_DIST_TILE (\d+)", src).group(1)) == _lib.IA3_TUNE_DIST_TILE

@@ -9,12 +9,9 @@ import numpy as np
 import pytest
 
 import np_oracle as O
+from imageanalysis3_amd._lib import IA3_TUNE_SEED_BGORDER, IA3_TUNE_SEED_DENSE, IA3_TUNE_COL_RTC
 
 pytestmark = pytest.mark.gpu
-
-IA3_TUNE_SEED_BGORDER = 18
-IA3_TUNE_SEED_DENSE = 4
-IA3_TUNE_COL_RTC = 17
 
 SHAPE = (25, 96, 128)   # a paired column-kernel depth; rows of 128: strip bound; X = 96: interior and border candidates
 SPOTS = [(8, 40, 40), (12, 48, 96), (17, 70, 30), (10, 6, 70)]

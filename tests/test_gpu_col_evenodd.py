@@ -20,7 +20,7 @@ DEPTHS = (50, 33)
 
 def _set_gauss_cert(v):
     from imageanalysis3_amd import _lib as L
-    L.check(L.lib().ia3_set_tuning(C.c_int(1), C.c_int(v)))
+    L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_GAUSS_CERT, C.c_int(v)))
 
 
 @functools.lru_cache(maxsize=None)

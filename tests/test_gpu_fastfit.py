@@ -15,12 +15,12 @@ import pytest
 
 from conftest import load_golden
 from harness import fastfit_ref as FR
+from imageanalysis3_amd._lib import IA3_TUNE_FIT_NBLIST
 
 pytestmark = pytest.mark.gpu
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 META = json.load(open(os.path.join(HERE, "golden", "fastfit.json")))
-IA3_TUNE_FIT_NBLIST = 5
 
 
 @pytest.fixture(scope="module")

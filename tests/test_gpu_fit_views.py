@@ -27,12 +27,12 @@ import pytest
 
 from conftest import build_case, build_legacy, load_golden
 from harness import fit_views_ref as VR
+from imageanalysis3_amd._lib import IA3_TUNE_FIT_NBLIST
 
 pytestmark = pytest.mark.gpu
 
 FIXTURES = ["edge_f32", "clu_f32", "c1_u16"]
 RADIUS = 5
-IA3_TUNE_FIT_NBLIST = 5
 
 # largest relative difference between ims_rec and the host model at the same records, over all seeds of the fixtures
 MEASURED_REC_MODEL = 1.79e-15
@@ -458,7 +458,7 @@ def test_multi_field_fitter_is_refused():
             with pytest.raises(NotImplementedError):
                 L.check(lib.ia3_fit_view_voxels(h, L.ptr(cnt), L.ptr(cnt), L.dptr(out)))
             with pytest.raises(NotImplementedError):
-                L.check(lib.ia3_fit_view_recs(h, 1, L.ptr(cnt), L.ptr(cnt), L.dptr(out), None))
+                L.check(lib.ia3_fit_view_recs(h, 1, L.ptr(cnt), L.ptr(cnt.view(np.uint8)), L.dptr(out), None))
             st = C.c_void_p()
             with pytest.raises(NotImplementedError):
                 L.check(lib.ia3_fit_view_residual_dev(h, 1, C.byref(st)))

@@ -306,14 +306,14 @@ def test_neighbour_scan_equals_neighbour_list():
     res = []
     try:
         for cap in (64, 2, 0):
-            L.check(L.lib().ia3_set_tuning(5, cap))      # IA3_TUNE_FIT_NBLIST
+            L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FIT_NBLIST, cap))
             f = iter_fit_seed_points(im, seeds.T)
             f.firstfit()
             first, nvox = np.array(f.ps), np.array(f.nvox)
             f.repeatfit()
             res.append((first, nvox, np.array(f.ps), f.n_iter))
     finally:
-        L.check(L.lib().ia3_set_tuning(5, 64))
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FIT_NBLIST, 64))
     assert res[0][3] >= 4
     for r in res[1:]:
         assert np.array_equal(r[1], res[0][1]) and r[3] == res[0][3]
@@ -356,7 +356,7 @@ def test_dense_grid_beyond_neighbour_list_vs_oracle():
 
 def _seed_dense(on):
     from imageanalysis3_amd import _lib as L
-    L.check(L.lib().ia3_set_tuning(4, 1 if on else 0))   # IA3_TUNE_SEED_DENSE
+    L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_SEED_DENSE, 1 if on else 0))
 
 
 def test_lazy_background_filter_equals_dense_filter():
@@ -433,20 +433,20 @@ def test_lazy_background_filter_equals_dense_filter():
             lazy = get_seeds(im, return_h=True, **kw)
             assert dense.shape == lazy.shape and np.array_equal(dense, lazy), (name, dense.shape, lazy.shape)
             if im.shape[0] in (30, 40, 50):
-                L.check(L.lib().ia3_set_tuning(C.c_int(8), C.c_int(0)))
+                L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_GAUSS_FOLD, C.c_int(0)))
                 lazy0 = get_seeds(im, return_h=True, **kw)
-                L.check(L.lib().ia3_set_tuning(C.c_int(8), C.c_int(1)))
+                L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_GAUSS_FOLD, C.c_int(1)))
                 assert dense.shape == lazy0.shape and np.array_equal(dense, lazy0), (name, "separate filters", dense.shape, lazy0.shape)
-                L.check(L.lib().ia3_set_tuning(C.c_int(9), C.c_int(0)))
+                L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_SEED_STRIPS, C.c_int(0)))
                 lazy1 = get_seeds(im, return_h=True, **kw)
-                L.check(L.lib().ia3_set_tuning(C.c_int(9), C.c_int(1)))
+                L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_SEED_STRIPS, C.c_int(1)))
                 assert dense.shape == lazy1.shape and np.array_equal(dense, lazy1), (name, "per-plane block minima", dense.shape, lazy1.shape)
             if not name.endswith("zeros_f32"):
                 assert len(dense) > 0, name
     finally:
         _seed_dense(False)
-        L.check(L.lib().ia3_set_tuning(C.c_int(8), C.c_int(1)))
-        L.check(L.lib().ia3_set_tuning(C.c_int(9), C.c_int(1)))
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_GAUSS_FOLD, C.c_int(1)))
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_SEED_STRIPS, C.c_int(1)))
 
 
 def test_phase_correlation_real_transforms_equal_complex_transforms():
@@ -464,14 +464,14 @@ def test_phase_correlation_real_transforms_equal_complex_transforms():
         for ref, src in cases:
             for norm in (None, "phase"):
                 for up in (1, 100):
-                    L.check(L.lib().ia3_set_tuning(6, 1))      # IA3_TUNE_FFT_C2C
+                    L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FFT_C2C, 1))
                     s0, e0, p0 = phase_cross_correlation(ref, src, upsample_factor=up, normalization=norm)
-                    L.check(L.lib().ia3_set_tuning(6, 0))
+                    L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FFT_C2C, 0))
                     s1, e1, p1 = phase_cross_correlation(ref, src, upsample_factor=up, normalization=norm)
                     assert np.abs(np.asarray(s0) - np.asarray(s1)).max() <= 1e-9, (ref.shape, ref.dtype, norm, up, s0, s1)
                     assert abs(e0 - e1) <= 1e-7 and abs(p0 - p1) <= 1e-7, (ref.shape, norm, up, e0, e1, p0, p1)
     finally:
-        L.check(L.lib().ia3_set_tuning(6, 0))
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FFT_C2C, 0))
 
 
 def test_fit_fovs_batch_entry():
@@ -520,13 +520,13 @@ def test_fused_first_fit_and_sweep1_equal_separate_positions():
     res = {}
     try:
         for mode in (0, 1):
-            L.check(L.lib().ia3_set_tuning(7, mode))      # IA3_TUNE_FIT_FUSE
+            L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FIT_FUSE, mode))
             for name, im in cases:
                 sp, keep = L.make_seed_params(th.get(name, 600.0), max_num_seeds=None)
                 tabs, info = L.fit_fovs([im], sp, fp, in_flight=1)
                 res[(mode, name)] = (tabs[0], info[0])
     finally:
-        L.check(L.lib().ia3_set_tuning(7, 1))
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FIT_FUSE, 1))
     for name, im in cases:
         (ta, ia), (tb, ib) = res[(0, name)], res[(1, name)]
         assert ia == ib, (name, ia, ib)

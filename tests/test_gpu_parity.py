@@ -306,13 +306,13 @@ def test_voronoi_tie_query_overflow_is_finished_on_the_host():
         im = build_case(name)
         ref = fit_fov_image(im, "647", th_seed=600, max_num_seeds=None, verbose=False)
         try:
-            L.check(L.lib().ia3_set_tuning(C.c_int(13), C.c_int(1)))
+            L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FIT_KDQ, C.c_int(1)))
             got = fit_fov_image(im, "647", th_seed=600, max_num_seeds=None, verbose=False)
             f = iter_fit_seed_points(im, g["seeds_h"][:, :3].T, radius_fit=5)
             f.firstfit()
             assert np.array_equal(f.nvox, g["first_nvox"]), name       # the Voronoi cells are the reference's
         finally:
-            L.check(L.lib().ia3_set_tuning(C.c_int(13), C.c_int(24)))
+            L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FIT_KDQ, C.c_int(24)))
         assert np.array_equal(got, ref), name
         assert got.shape == g["table"].shape
 
@@ -328,11 +328,11 @@ def test_dependency_wait_abort_is_reported_and_the_library_recovers():
     g = load_golden("fit_club_f32.npz")
     im = build_case("club_f32")
     try:
-        L.check(L.lib().ia3_set_tuning(C.c_int(101), C.c_int(16)))
+        L.check(L.lib().ia3_set_tuning(L.IA3_DEBUG_FIT_WAITBOUND, C.c_int(16)))
         with pytest.raises(L.IA3Error, match="dependency wait exceeded its bound"):
             fit_fov_image(im, "647", th_seed=600, max_num_seeds=None, verbose=False)
     finally:
-        L.check(L.lib().ia3_set_tuning(C.c_int(101), C.c_int(0)))
+        L.check(L.lib().ia3_set_tuning(L.IA3_DEBUG_FIT_WAITBOUND, C.c_int(0)))
     t = fit_fov_image(im, "647", th_seed=600, max_num_seeds=None, verbose=False)
     assert t.shape == g["table"].shape
     assert_rows_close(t, g["table"])
@@ -354,11 +354,11 @@ def test_refit_with_unchanged_neighbours_is_not_repeated():
     res = {}
     try:
         for memo in (1, 0):
-            L.check(L.lib().ia3_set_tuning(C.c_int(14), C.c_int(memo)))
+            L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FIT_MEMO, C.c_int(memo)))
             res[memo] = [L.fit_fovs([im], sp, fp, in_flight=1) for im in ims]
             res[memo].append(L.fit_fovs(ims[4:8], sp, fp, in_flight=4))     # the uint16 ones as one group fit
     finally:
-        L.check(L.lib().ia3_set_tuning(C.c_int(14), C.c_int(1)))
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_FIT_MEMO, C.c_int(1)))
     saved = 0
     for (t1, i1), (t0, i0) in zip(res[1], res[0]):
         for a, b, ia, ib in zip(t1, t0, i1, i0):
@@ -675,12 +675,12 @@ def test_warp_cubic_one_pass_prefilter_and_grouped_gather_bit_exact(dtype):
         ref = O.warp_3d_image(im, drift, fld, 3, "nearest")
         try:
             for knob in (64, 1, 3, 9, 32, 0, -1):
-                L.check(L.lib().ia3_set_tuning(12, knob))      # IA3_TUNE_WARP_ONEPASS
+                L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_WARP_ONEPASS, knob))
                 w = warp_3d_image(im, drift, fld, 3, "nearest")
                 assert w.dtype == ref.dtype
                 assert np.array_equal(w.view(view), ref.view(view)), (drift, fld is not None, knob)
         finally:
-            L.check(L.lib().ia3_set_tuning(12, 64))
+            L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_WARP_ONEPASS, 64))
 
 
 @pytest.mark.parametrize("dtype", [np.uint16, np.float32])
@@ -1194,7 +1194,7 @@ def test_fit_fovs_waits_for_stacks_still_in_production_on_the_callers_stream():
 def _set_gauss_cert(v):
     import ctypes as C
     from imageanalysis3_amd import _lib as L
-    L.check(L.lib().ia3_set_tuning(C.c_int(1), C.c_int(v)))
+    L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_GAUSS_CERT, C.c_int(v)))
 
 
 def test_gaussian_long_filter_certified_fused_path_bit_exact():
@@ -1270,7 +1270,7 @@ def test_gaussian_axis0_folded_column_pass_bit_exact():
                 for mode in ("reflect", "nearest"):
                     ref = ndi.gaussian_filter(im, 7.5, mode=mode, truncate=4.0)
                     for fold, cert in ((1, -2), (1, -1), (1, 1 << 28), (0, -2)):
-                        L.check(L.lib().ia3_set_tuning(C.c_int(8), C.c_int(fold)))
+                        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_GAUSS_FOLD, C.c_int(fold)))
                         _set_gauss_cert(cert)
                         got = gaussian_filter(im, 7.5, mode=mode, truncate=4.0)
                         if im.dtype == np.float32:
@@ -1280,7 +1280,7 @@ def test_gaussian_axis0_folded_column_pass_bit_exact():
                         assert same, (Z, name, mode, fold, cert, int((got != ref).sum()))
     finally:
         _set_gauss_cert(-2)
-        L.check(L.lib().ia3_set_tuning(C.c_int(8), C.c_int(1)))
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_GAUSS_FOLD, C.c_int(1)))
 
 
 def test_dog_filter_pair_shared_axis0_launch_bit_exact():
@@ -1781,11 +1781,11 @@ def test_upsampled_dft_on_matrix_cores_equals_vector_unit():
         cases += [(ref, src), (ref.astype(np.uint16), src.astype(np.uint16))]
     try:
         for valu in (0, 1):
-            L.check(L.lib().ia3_set_tuning(C.c_int(2), C.c_int(valu)))
+            L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_DFT_VALU, C.c_int(valu)))
             out[valu] = [alignment.phase_cross_correlation(a, b, upsample_factor=up, normalization=nm)
                          for a, b in cases for up in (10, 100) for nm in (None, "phase")]
     finally:
-        L.check(L.lib().ia3_set_tuning(C.c_int(2), C.c_int(0)))
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_DFT_VALU, C.c_int(0)))
     for (s0, e0, p0), (s1, e1, p1) in zip(out[0], out[1]):
         assert np.array_equal(s0, s1), (s0, s1)
         assert abs(e0 - e1) <= 1e-9 and abs(p0 - p1) <= 1e-9

@@ -308,11 +308,11 @@ def test_fit_spots_by_segmentation_compiles_nothing(tmp_path, capfd, monkeypatch
     lab[3:18, 34:62, 2:62] = 2   # depth 17
     with L.DeviceStack.upload(im) as st:
         got_s, got_i = fit_spots_by_segmentation(st, "647", lab, th_seed=300)
-        L.check(L.lib().ia3_set_tuning(8, 0))
+        L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_GAUSS_FOLD, 0))
         try:
             want_s, want_i = R.fit_in_labels(st, "647", lab, np.zeros(3), th_seed=300)
         finally:
-            L.check(L.lib().ia3_set_tuning(8, 1))
+            L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_GAUSS_FOLD, 1))
     assert len(got_s) > 0 and set(got_i.tolist()) == {1, 2}
     assert _same(got_s, want_s) and _same(got_i, want_i)
     assert list(tmp_path.iterdir()) == []

@@ -6,11 +6,9 @@ float32, row lengths with and without the column kernel's strip minima, and the 
 import ctypes as C
 import numpy as np
 import pytest
+from imageanalysis3_amd._lib import IA3_TUNE_SEED_FUSED, IA3_TUNE_SEED_DENSE
 
 pytestmark = pytest.mark.gpu
-
-IA3_TUNE_SEED_FUSED = 15
-IA3_TUNE_SEED_DENSE = 4
 
 
 def _tune(key, value):

@@ -71,7 +71,7 @@ def fused_units():
 
 def seed_dense(on):
     from imageanalysis3_amd import _lib as L
-    L.check(L.lib().ia3_set_tuning(4, 1 if on else 0))   # IA3_TUNE_SEED_DENSE
+    L.check(L.lib().ia3_set_tuning(L.IA3_TUNE_SEED_DENSE, 1 if on else 0))
 
 
 # ---- windows -------------------------------------------------------------------------------------------------------------

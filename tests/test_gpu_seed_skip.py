@@ -9,11 +9,9 @@ without strip outputs (nothing skipped)."""
 import ctypes as C
 import numpy as np
 import pytest
+from imageanalysis3_amd._lib import IA3_TUNE_SEED_SKIP, IA3_TUNE_SEED_DENSE
 
 pytestmark = pytest.mark.gpu
-
-IA3_TUNE_SEED_SKIP = 16
-IA3_TUNE_SEED_DENSE = 4
 
 
 def _tune(key, value):

@@ -213,17 +213,8 @@ def test_ctypes_mirrors_match_the_header():
     src = open(os.path.join(ROOT, "include", "ia3.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
     lib = _lib.lib()
-    for name, nargs in {"ia3_assign_nearest_dev": 5, "ia3_select_chromosomes_dev": 13}.items():
-        m = re.search(r"\b%s\s*\(([^)]*)\)" % name, src)
-        assert m and len(m.group(1).split(",")) == nargs, name
-        assert name in _lib.EXPORTS and hasattr(lib, name)
-    # the wrappers pass as many arguments as the header declares
-    import textwrap
-    for wrapper, name, nargs in ((_lib.assign_nearest, "ia3_assign_nearest_dev", 5),
-                                 (_lib.select_chromosomes, "ia3_select_chromosomes_dev", 13)):
-        tree = ast.parse(textwrap.dedent(inspect.getsource(wrapper)))
-        calls = [n for n in ast.walk(tree) if isinstance(n, ast.Call) and isinstance(n.func, ast.Attribute) and n.func.attr == name]
-        assert len(calls) == 1 and len(calls[0].args) == nargs and not calls[0].keywords, name
+    for name in ("ia3_assign_nearest_dev", "ia3_select_chromosomes_dev"):      # prototypes and arity: test_abi_cpu.py
+        assert re.search(r"\b%s\s*\(" % name, src) and name in _lib.EXPORTS and hasattr(lib, name)
     for define, value in (("IA3_SELECT_THREADS", _lib.SELECT_THREADS), ("IA3_SELECT_TILE", _lib.SELECT_TILE),
                           ("IA3_SELECT_EMPTY", _lib.IA3_SELECT_EMPTY)):
         assert int(re.search(r"#define\s+%s\s+(\d+)" % define, src).group(1)) == value
