@@ -7,13 +7,15 @@
 // within pix, neighbours taken modulo the shape` runs on LDS tiles whose halo is fetched through the wrapped index;
 // survivors are appended by ballot + one integer atomic per wave and put in order on the host (they are few).
 //
-// Moment fits.  One wavefront per seed, up to FF_SLOTS ball offsets per lane.  The wave drops the offsets that
+// Moment fits.  One wavefront per seed, up to BALL_SLOTS ball offsets per lane (ia3_ball.h).  The wave drops the offsets that
 // belong to another seed's Voronoi cell (neighbour list, or a scan of the seed list for crowded seeds), gathers the
 // voxels inside the image into LDS in ball order (ballot ranks), optionally re-centres on their first maximum, finds the
 // order-statistic background by rank counting and leaves the sums to a few lanes that add serially in NumPy's order
 // (ia3_fastfit.h, ia3_npsum.h): 254 additions per sum, where the order matters and the width does not.
 #include "ia3_rt.h"
 #include "ia3_fastfit.h"
+#include "ia3_ball.h"
+#include "ia3_wave.h"
 #include <algorithm>
 #include <math.h>
 
@@ -81,7 +83,7 @@ __global__ __launch_bounds__(256) void ff_seed_k(const T* __restrict__ im, int Z
     tile[e] = (float)im[((size_t)wrap(z0 - pix + p, Z) * X + wrap(x0 - pix + r, X)) * Y + wrap(y0 - pix + c, Y)];
   }
   __syncthreads();
-  const int ly = threadIdx.x & 63, lx = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int ly = threadIdx.x & 63, lx = threadIdx.x >> 6;
   for (int lz = 0; lz < SD_TZ; ++lz) {
     const int z = z0 + lz, x = x0 + lx, y = y0 + ly;
     bool keep = z < Z && x < X && y < Y;
@@ -95,63 +97,37 @@ __global__ __launch_bounds__(256) void ff_seed_k(const T* __restrict__ im, int Z
           for (int dy = 0; dy <= 2 * pix; ++dy) keep = keep && v >= row[dy];
         }
     }
-    const unsigned long long m = __ballot(keep);
-    if (m) {
-      const int leader = __ffsll((long long)m) - 1;
-      unsigned base = 0;
-      if (lane == leader) base = atomicAdd(count, (unsigned)__popcll(m));
-      base = __shfl(base, leader);
-      if (keep) {
-        const unsigned pos = base + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
-        if (pos < cap) hits[pos] = SeedHit{((long long)z * X + x) * Y + y, v, 0};
-      }
-    }
+    const unsigned pos = ia3::wave_append(count, keep);
+    if (keep && pos < cap) hits[pos] = SeedHit{((long long)z * X + x) * Y + y, v, 0};
   }
 }
 
 // ---- neighbour lists: one wave per seed scans all seeds 64 at a time; ballot + prefix rank, so every list is in
 // ascending index order (what query_ball_tree returns, self left out here) ---------------------------------------
-constexpr int FF_MAXNB = 64;
-
 __global__ __launch_bounds__(256) void ff_nbr_k(const double* __restrict__ seeds, int n, double r2, int* __restrict__ cnt,
                                                 int* __restrict__ idx) {
   const int lane = threadIdx.x & 63;
   const int i = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (i >= n) return;   // whole wave leaves together
-  const double cz = seeds[3 * i], cx = seeds[3 * i + 1], cy = seeds[3 * i + 2];
   int c = 0;
-  for (int j0 = 0; j0 < n; j0 += 64) {
-    const int j = j0 + lane;
-    bool hit = false;
-    if (j < n && j != i) {
-      const double a = cz - seeds[3 * j], b = cx - seeds[3 * j + 1], d = cy - seeds[3 * j + 2];
-      hit = a * a + b * b + d * d <= r2;
-    }
-    const unsigned long long m = __ballot(hit);
+  ia3::scan_seeds(seeds, 0, n, i, r2, [&](int j0, unsigned long long m, bool hit) {
     if (hit) {
-      const int pos = c + __popcll(m & ((1ull << lane) - 1ull));
-      if (pos < FF_MAXNB) idx[(size_t)i * FF_MAXNB + pos] = j;
+      const int pos = c + ia3::lane_rank(m);
+      if (pos < ia3::BALL_NBLIST) idx[(size_t)i * ia3::BALL_NBLIST + pos] = j0 + lane;
     }
     c += __popcll(m);
-  }
-  if (lane == 0) cnt[i] = c;   // not clamped: > FF_MAXNB = the list overflowed, the consumer scans
+    return true;
+  });
+  if (lane == 0) cnt[i] = c;   // not clamped: > BALL_NBLIST = the list overflowed, the consumer scans
 }
 
 // ---- moment fit ----------------------------------------------------------------------------------------------------
-constexpr int FF_SLOTS = ia3::FF_MAXVOX / 64;
-
 struct FfLds {
   double v[ia3::FF_MAXVOX];      // voxel values, list order
   double wn[ia3::FF_MAXVOX];     // normalised weights
   int x[3][ia3::FF_MAXVOX];      // voxel coordinates
   double bk, h, c[3];
 };
-
-struct BallOff { int dz, dx, dy; };
-__device__ __forceinline__ BallOff ball_off(const int* __restrict__ ball, int vi) {
-  const int w = ball[vi];
-  return BallOff{(int)(signed char)(w & 0xff), (int)(signed char)((w >> 8) & 0xff), (int)(signed char)((w >> 16) & 0xff)};
-}
 
 // the 12 numbers of gfit_fast from the n voxels in LDS (n <= FF_MAXVOX); called by every lane of the wave
 __device__ __forceinline__ void moments_from_lds(FfLds* L, int n, double bk_f, int kind, double* __restrict__ out) {
@@ -198,57 +174,34 @@ __global__ __launch_bounds__(64) void ff_moment_k(MomentArgs a) {
   const double c0 = a.centers[3 * i], c1 = a.centers[3 * i + 1], c2 = a.centers[3 * i + 2];
   int iz = (int)c0, ix = (int)c1, iy = (int)c2;   // Python int(): toward zero
 
-  // ball offsets of this lane that stay with this seed (bit s = offset lane + 64 s)
+  // ball offsets of this lane that stay with this seed (bit s = slot s)
+  ia3::SeedBall sb{a.ball, a.nball, iz, ix, iy, a.Z, a.X, a.Y};
   unsigned own = 0;
-  for (int s = 0; s < FF_SLOTS; ++s)
-    if (lane + 64 * s < a.nball) own |= 1u << s;
-  if (a.avoid) {
-    auto against = [&](int j) {   // wave-uniform j != i: argmin over the ascending neighbour list takes the first minimum
+  for (int s = 0; s < ia3::BALL_SLOTS; ++s)
+    if (sb.has(s)) own |= 1u << s;
+  if (a.avoid)
+    ia3::each_neighbour(a.centers, i, a.nbr_cnt, a.nbr_idx, a.nb_cap, a.nb_r2, [&]() { return ia3::SeedRange{0, a.n}; }, [&](int j) {
+      // wave-uniform j != i: argmin over the ascending neighbour list takes the first minimum
       const double dz = a.centers[3 * j] - c0, dx = a.centers[3 * j + 1] - c1, dy = a.centers[3 * j + 2] - c2;
-      for (int s = 0; s < FF_SLOTS; ++s) {
-        const int vi = lane + 64 * s;
-        if (vi < a.nball) {
-          const BallOff o = ball_off(a.ball, vi);
+      for (int s = 0; s < ia3::BALL_SLOTS; ++s)
+        if (sb.has(s)) {
+          const ia3::BallOff o = sb.off(s);
           if (ia3::ff_loses(dz, dx, dy, o.dz, o.dx, o.dy, j < i)) own &= ~(1u << s);
         }
-      }
-    };
-    const int cnt = a.nbr_cnt[i];
-    if (cnt <= a.nb_cap) {
-      for (int q = 0; q < cnt; ++q) against(a.nbr_idx[(size_t)i * FF_MAXNB + q]);
-    } else {
-      for (int j0 = 0; j0 < a.n; j0 += 64) {
-        const int j = j0 + lane;
-        bool hit = false;
-        if (j < a.n && j != i) {
-          const double p = c0 - a.centers[3 * j], q = c1 - a.centers[3 * j + 1], r = c2 - a.centers[3 * j + 2];
-          hit = p * p + q * q + r * r <= a.nb_r2;
-        }
-        unsigned long long m = __ballot(hit);
-        while (m) {
-          const int b = __ffsll((long long)m) - 1;
-          m &= m - 1;
-          against(j0 + b);
-        }
-      }
-    }
-  }
+      return true;
+    });
 
   int n = 0;
   for (int pass = 0; pass < 2; ++pass) {
     n = 0;
-    for (int s = 0; s < FF_SLOTS; ++s) {
-      const int vi = lane + 64 * s;
+    sb.iz = iz; sb.ix = ix; sb.iy = iy;   // pass 1: re-centred
+    for (int s = 0; s < ia3::BALL_SLOTS; ++s) {
       bool in = false;
       int z = 0, x = 0, y = 0;
-      if (vi < a.nball && ((own >> s) & 1u)) {
-        const BallOff o = ball_off(a.ball, vi);
-        z = iz + o.dz; x = ix + o.dx; y = iy + o.dy;
-        in = z >= 0 && z < a.Z && x >= 0 && x < a.X && y >= 0 && y < a.Y;
-      }
+      if ((own >> s) & 1u) sb.voxel(s, [&](int vz, int vx, int vy, bool inside) { z = vz; x = vx; y = vy; in = inside; });
       const unsigned long long m = __ballot(in);
       if (in) {
-        const int pos = n + __popcll(m & ((1ull << lane) - 1ull));   // < nball <= FF_MAXVOX
+        const int pos = n + ia3::lane_rank(m);   // < nball <= FF_MAXVOX
         L.v[pos] = (double)im[((size_t)z * a.X + x) * a.Y + y];
         L.x[0][pos] = z; L.x[1][pos] = x; L.x[2][pos] = y;
       }
@@ -291,16 +244,6 @@ __global__ __launch_bounds__(64) void ff_voxels_k(const double* __restrict__ val
   }
   __syncthreads();
   moments_from_lds(&L, n, bk_f, kind, out12);
-}
-
-// offsets of the reference's ball, in its order: [-r, r) per axis, d^2 <= r^2 (Fitting_v4.py:506-508), packed bytes
-int make_ball(int r, std::vector<int>& ball) {
-  ball.clear();
-  for (int z = -r; z < r; ++z)
-    for (int x = -r; x < r; ++x)
-      for (int y = -r; y < r; ++y)
-        if (z * z + x * x + y * y <= r * r) ball.push_back((z & 0xff) | ((x & 0xff) << 8) | ((y & 0xff) << 16));
-  return (int)ball.size();
 }
 
 template <class T>
@@ -425,16 +368,17 @@ int ia3_fastfit_moments_dev(const ia3_stack* im, const double* centers_zxy, int 
   if (radius_fit < 1) return set_error(IA3_EINVAL, "radius_fit must be >= 1");
   if (!(bk_f >= 0.0 && bk_f < 1.0)) return set_error(IA3_EINVAL, "bk_f must lie in [0, 1)");
   std::vector<int> ball;
-  const int nball = radius_fit <= 5 ? make_ball(radius_fit, ball) : ia3::FF_MAXVOX + 1;
+  const int nball = radius_fit <= 5 ? ia3::ball_build(radius_fit, ball) : ia3::FF_MAXVOX + 1;
   if (nball > ia3::FF_MAXVOX)
     return set_error(IA3_EUNSUPPORTED, "fast_fit_big_image: radius_fit %d gives more than %d voxels per ball", radius_fit, ia3::FF_MAXVOX);
   if (n == 0) return IA3_OK;
+  if (n > 0x7fffffff / ia3::BALL_NBLIST) return set_error(IA3_EUNSUPPORTED, "too many seeds");   // each_neighbour indexes with int
   for (int k = 0; k < 3 * n; ++k)
     if (!(fabs(centers_zxy[k]) < 1e9)) return set_error(IA3_EINVAL, "centre %d is not a finite voxel position", k / 3);
   hipStream_t st = stream();
   const size_t nn = (size_t)n;
   Scratch dcen(nn * 3 * sizeof(double)), dball((size_t)nball * sizeof(int)), dout(nn * 12 * sizeof(double)),
-      dcnt(nn * sizeof(int)), didx(avoid_neighbors ? nn * FF_MAXNB * sizeof(int) : 16),
+      dcnt(nn * sizeof(int)), didx(avoid_neighbors ? nn * ia3::BALL_NBLIST * sizeof(int) : 16),
       dvc(vox_count ? nn * sizeof(int) : 16), dvv(vox_count ? nn * nball * sizeof(double) : 16),
       dvx(vox_count ? nn * nball * 3 * sizeof(int) : 16);
   if (!dcen.p || !dball.p || !dout.p || !dcnt.p || !didx.p || !dvc.p || !dvv.p || !dvx.p) return IA3_ENOMEM;

@@ -13,7 +13,7 @@
 //              never materialised: data(v) = im(v) - Σ_{j≠i} rec_j(v) is rebuilt from the neighbours'
 //              parameter vectors, which is the same quantity up to f64 rounding order.
 //
-// Wave layout: the ball has <= 512 voxels (radius 5: 512) = 8 slots per lane.  Per LM evaluation a
+// Wave layout: the ball has <= 512 voxels (radius 5: 512) = 8 slots per lane (the map: ia3_ball.h).  Per LM evaluation a
 // lane computes residual + float32-rounded Jacobian row for its slots (float64, as NumPy does for
 // the reference under numpy>=2) and accumulates its share of JᵀJ (55) and Jᵀr (10); permlane swaps
 // and DPP rotations sum across the wave.  The 10x10 trust-region algebra (ia3_lm.h) runs redundantly on
@@ -25,6 +25,8 @@
 #include "ia3_lm.h"
 #include "ia3_init.h"
 #include "ia3_kdtree.h"
+#include "ia3_ball.h"
+#include "ia3_wave.h"
 #include <algorithm>
 #include <numeric>
 #include <math.h>
@@ -45,9 +47,7 @@ void kd_build(const double* points, int n, std::vector<ia3::KdNode>& nodes, std:
 
 namespace {
 
-constexpr int SLOTS = 8;  // voxel slots per lane
-constexpr int MAXNB = 64; // neighbour slots per seed (seeds within 2r); denser seeds re-scan the seed list instead
-constexpr int MAXBALL = 64 * SLOTS;
+constexpr int SLOTS = BALL_SLOTS, MAXBALL = BALL_MAXVOX;   // ia3_ball.h
 
 struct SeedState {
   double x[NP];   // unconstrained parameters of the last successful fit
@@ -71,10 +71,10 @@ struct FitArgs {
   const double* seeds;      // n x 3
   int n;                    // number of seeds (all fields)
   int fuse;                 // a seed without neighbours: first fit and sweep 1 by the same wave (see fit_stages_k)
-  int nb_cap;               // lists longer than this are not used (MAXNB; lowered by IA3_TUNE_FIT_NBLIST in tests)
+  int nb_cap;               // lists longer than this are not used (BALL_NBLIST; lowered by IA3_TUNE_FIT_NBLIST in tests)
   double nb_r2;             // (2r)²: seeds closer than this interact
-  const int* nbr_cnt;       // n: number of neighbours of seed i (NOT clamped: > MAXNB = list overflow, see each_neighbour)
-  const int* nbr_idx;       // n x MAXNB: the first MAXNB seeds j != i with |c_i - c_j|² <= (2r)², ascending
+  const int* nbr_cnt;       // n: number of neighbours of seed i (NOT clamped: > BALL_NBLIST = list overflow, see each_neighbour)
+  const int* nbr_idx;       // n x BALL_NBLIST: the first BALL_NBLIST seeds j != i with |c_i - c_j|² <= (2r)², ascending
   const int* ball;          // nball packed offsets (dz, dx, dy, 0) as signed bytes, np.indices order: one load per voxel
   const unsigned long long* tie_lost;  // n x SLOTS lane masks: voxels this seed loses in an exact Voronoi tie (voronoi_ties_k); may be null
   int nball, radius;
@@ -648,20 +648,6 @@ __device__ __forceinline__ void store_result(const FitArgs& fa, int i, IA3_LDS W
   }
 }
 
-// Squared distance as scipy's cKDTree forms it (query.cxx: s = 0; s += d_k * d_k for k = 0, 1, 2; separate multiply and
-// add): the Voronoi decisions compare these values for equality, so no contraction into fused multiply-adds here.
-__device__ __forceinline__ double dist2_seq(double az, double ax, double ay, double bz, double bx, double by) {
-  const double d0 = az - bz, d1 = ax - bx, d2 = ay - by;
-  return __dadd_rn(__dadd_rn(__dmul_rn(d0, d0), __dmul_rn(d1, d1)), __dmul_rn(d2, d2));
-}
-
-// offsets of ball voxel vi from the truncated seed position (packed signed bytes dz, dx, dy)
-struct BallOff { int dz, dx, dy; };
-__device__ __forceinline__ BallOff ball_off(const int* __restrict__ ball, int vi) {
-  const int w = ball[vi];
-  return BallOff{(int)(signed char)(w & 0xff), (int)(signed char)((w >> 8) & 0xff), (int)(signed char)((w >> 16) & 0xff)};
-}
-
 struct StageCtl;
 // ---- neighbour lists on the device: one wave per seed scans all seeds 64 at a time; hits are appended with
 // ballot + prefix rank, so every list comes out in ascending index order (5 k seeds: 25 M distance tests, ~10 µs;
@@ -680,41 +666,26 @@ __global__ __launch_bounds__(256) void nbr_build_k(const double* __restrict__ se
   const int fov = fov_of[i];
   const int first = fov_start[fov], n = fov_start[fov + 1];   // candidates: the seeds of the same field
   if (i >= n) return;   // a grid sized for a capacity (the count was still on the device at launch time)
-  const double cz = seeds[3 * i], cx = seeds[3 * i + 1], cy = seeds[3 * i + 2];
-  const int iz = (int)cz, ix = (int)cx, iy = (int)cy;
+  const double c0[3] = {seeds[3 * i], seeds[3 * i + 1], seeds[3 * i + 2]};
+  const SeedBall sb{ball, nball, (int)c0[0], (int)c0[1], (int)c0[2], Z, X, Y};
   int c = 0;
   bool tie = false;
-  for (int j0 = first; j0 < n; j0 += 64) {
-    const int j = j0 + lane;
-    bool hit = false;
-    if (j < n && j != i) {
-      const double a = cz - seeds[3 * j], b = cx - seeds[3 * j + 1], d = cy - seeds[3 * j + 2];
-      hit = a * a + b * b + d * d <= r2;
-    }
-    unsigned long long m = __ballot(hit);
+  scan_seeds(seeds, first, n, i, r2, [&](int j0, unsigned long long m, bool hit) {
     if (hit) {
-      const int pos = c + __popcll(m & ((1ull << lane) - 1ull));
-      if (pos < MAXNB) idx[(size_t)i * MAXNB + pos] = j;
+      const int pos = c + lane_rank(m);
+      if (pos < BALL_NBLIST) idx[(size_t)i * BALL_NBLIST + pos] = j0 + lane;
     }
     c += __popcll(m);
-    while (m) {   // wave-uniform: the ball of seed i against neighbour j0 + b
-      const int bj = __ffsll((long long)m) - 1;
-      m &= m - 1;
-      const double sz = seeds[3 * (j0 + bj)], sx = seeds[3 * (j0 + bj) + 1], sy = seeds[3 * (j0 + bj) + 2];
-      for (int s = 0; s < SLOTS; ++s) {
-        const int vi = lane + 64 * s;
-        if (vi < nball) {
-          const BallOff o = ball_off(ball, vi);
-          const int z = iz + o.dz, x = ix + o.dx, y = iy + o.dy;
-          if (z >= 0 && z < Z && x >= 0 && x < X && y >= 0 && y < Y)
-            tie |= dist2_seq(cz, cx, cy, (double)z, (double)x, (double)y) == dist2_seq(sz, sx, sy, (double)z, (double)x, (double)y);
-        }
-      }
-    }
-  }
+    return each_hit(j0, m, [&](int j) {   // wave-uniform: the ball of seed i against neighbour j
+      const double sj[3] = {seeds[3 * j], seeds[3 * j + 1], seeds[3 * j + 2]};
+      for (int s = 0; s < SLOTS; ++s)
+        sb.voxel(s, [&](int z, int x, int y, bool in) { if (in) tie |= voronoi_tied(c0, sj, z, x, y); });
+      return true;
+    });
+  });
   const bool any_tie = __ballot(tie) != 0ull;
   if (lane == 0) {
-    if (c > MAXNB) atomicMax(overflow, c);   // statistics only: consumers fall back to each_neighbour's scan
+    if (c > BALL_NBLIST) atomicMax(overflow, c);   // statistics only: consumers fall back to each_neighbour's scan
     cnt[i] = c;
     tie_flag[i] = any_tie ? 1 : 0;
     // (flags: a look before the atomic — a crowded field would otherwise send thousands of them to one word; the count of
@@ -727,37 +698,21 @@ __global__ __launch_bounds__(256) void nbr_build_k(const double* __restrict__ se
   }
 }
 
-// f(j) for every seed j != i within 2r of seed i, ascending j, wave-uniform.  Seeds with at most MAXNB neighbours read
-// their list; denser ones (the reference has no cap: Fitting_v4.py:601,612 query a cKDTree) scan the whole seed list,
-// 64 candidates per step with a ballot.  f returns false to stop early.
+// ia3_ball.h's iterator on a fitter's lists; a crowded seed scans the seeds of its own field (neighbours live there)
 template <class F>
 __device__ __forceinline__ void each_neighbour(const FitArgs& fa, int i, F f) {
-  const int cnt = fa.nbr_cnt[i];
-  if (cnt <= fa.nb_cap) {
-    for (int q = i * MAXNB; q < i * MAXNB + cnt; ++q)
-      if (!f(fa.nbr_idx[q])) return;
-    return;
-  }
-  const int lane = threadIdx.x & 63;
-  const double cz = fa.seeds[3 * i], cx = fa.seeds[3 * i + 1], cy = fa.seeds[3 * i + 2];
-  const int fov = fa.fov_of[i];
-  const int first = fa.fov_start[fov], last = fa.fov_start[fov + 1];   // neighbours live in the same field
-  for (int j0 = first; j0 < last; j0 += 64) {
-    const int j = j0 + lane;
-    bool hit = false;
-    if (j < last && j != i) {
-      const double a = cz - fa.seeds[3 * j], b = cx - fa.seeds[3 * j + 1], d = cy - fa.seeds[3 * j + 2];
-      hit = a * a + b * b + d * d <= fa.nb_r2;
-    }
-    unsigned long long m = __ballot(hit);
-    while (m) {
-      const int b = __ffsll((long long)m) - 1;
-      m &= m - 1;
-      if (!f(j0 + b)) return;
-    }
-  }
+  ia3::each_neighbour(fa.seeds, i, fa.nbr_cnt, fa.nbr_idx, fa.nb_cap, fa.nb_r2, [&]() {
+    const int fov = fa.fov_of[i];
+    return SeedRange{fa.fov_start[fov], fa.fov_start[fov + 1]};
+  }, f);
+}
+__device__ __forceinline__ SeedBall seed_ball(const FitArgs& fa, int i) {   // seed i's ball; Python int(): toward zero
+  return SeedBall{fa.ball, fa.nball, (int)fa.seeds[3 * i], (int)fa.seeds[3 * i + 1], (int)fa.seeds[3 * i + 2], fa.Z, fa.X, fa.Y};
 }
 
+// gather_first and gather_repeat, fit_stages_k's own, spell out what ia3_ball.h states as SeedBall::voxel, ball_voronoi
+// and in_ball: the kernel sits on the register cliff, and each of those helpers, inlined, gave it another instruction
+// stream and a measurably slower first fit.  With ball_vi, ball_count and each_neighbour the stream is what it was.
 // ---- stage 0 = firstfit of one seed (Fitting_v4.py:606-637) -----------------------------------------
 // the voxels of the seed's Voronoi cell inside its ball, from the ORIGINAL image; returns their number
 __device__ __forceinline__ int gather_first(const FitArgs& fa, int i, IA3_LDS BallLds* bl, unsigned& valid_out, double* vals) {
@@ -774,7 +729,7 @@ __device__ __forceinline__ int gather_first(const FitArgs& fa, int i, IA3_LDS Ba
       const double sz = fa.seeds[3 * j], sx = fa.seeds[3 * j + 1], sy = fa.seeds[3 * j + 2];
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s) {
-        const int vi = lane + 64 * s;
+        const int vi = ball_vi(lane, s);
         if (vi < fa.nball) {
           const BallOff o = ball_off(fa.ball, vi);
           const double z = (double)(iz + o.dz), x = (double)(ix + o.dx), y = (double)(iy + o.dy);
@@ -795,7 +750,7 @@ __device__ __forceinline__ int gather_first(const FitArgs& fa, int i, IA3_LDS Ba
   unsigned valid = 0;
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
-    const int vi = lane + 64 * s;
+    const int vi = ball_vi(lane, s);
     float fd = 0.f, fz = 0.f, fx = 0.f, fy = 0.f;
     vals[s] = 0.0;
     if (vi < fa.nball) {
@@ -812,9 +767,7 @@ __device__ __forceinline__ int gather_first(const FitArgs& fa, int i, IA3_LDS Ba
     bl->dat[s][lane] = fd; bl->cz[s][lane] = fz; bl->cx[s][lane] = fx; bl->cy[s][lane] = fy;
   }
   valid_out = valid;
-  return __popcll(__ballot(valid & 1u)) + __popcll(__ballot(valid & 2u)) + __popcll(__ballot(valid & 4u)) +
-         __popcll(__ballot(valid & 8u)) + __popcll(__ballot(valid & 16u)) + __popcll(__ballot(valid & 32u)) +
-         __popcll(__ballot(valid & 64u)) + __popcll(__ballot(valid & 128u));
+  return ball_count(valid);
 }
 
 // ---- exact Voronoi ties by the reference's rule (ia3_kdtree.h) -----------------------------------------------------
@@ -831,22 +784,12 @@ __global__ __launch_bounds__(64) void voronoi_ties_k(FitArgs fa, KdTree tree, in
   if (i >= seed0 + tree.n || !tie_flag[i]) return;
   const int lane = threadIdx.x & 63;
   const double c0[3] = {fa.seeds[3 * i], fa.seeds[3 * i + 1], fa.seeds[3 * i + 2]};
-  const int iz = (int)c0[0], ix = (int)c0[1], iy = (int)c0[2];
+  const SeedBall sb = seed_ball(fa, i);
   unsigned lost = 0, tied = 0;
   each_neighbour(fa, i, [&](int j) {
-    const double sz = fa.seeds[3 * j], sx = fa.seeds[3 * j + 1], sy = fa.seeds[3 * j + 2];
-#pragma unroll
-    for (int s = 0; s < SLOTS; ++s) {
-      const int vi = lane + 64 * s;
-      if (vi < fa.nball) {
-        const BallOff o = ball_off(fa.ball, vi);
-          const double z = (double)(iz + o.dz), x = (double)(ix + o.dx), y = (double)(iy + o.dy);
-        const double dme = dist2_seq(c0[0], c0[1], c0[2], z, x, y);
-        const double dj = dist2_seq(sz, sx, sy, z, x, y);
-        if (dj < dme) lost |= 1u << s;
-        else if (dj == dme) tied |= 1u << s;
-      }
-    }
+    const double sj[3] = {fa.seeds[3 * j], fa.seeds[3 * j + 1], fa.seeds[3 * j + 2]};
+    const BallSplit bs = ball_voronoi(sb, c0, sj);
+    lost |= bs.lost; tied |= bs.tied;
     return true;
   });
   tied &= ~lost;   // a strictly nearer seed decides without the tree
@@ -854,18 +797,15 @@ __global__ __launch_bounds__(64) void voronoi_ties_k(FitArgs fa, KdTree tree, in
 #pragma unroll 1
   for (int s = 0; s < SLOTS; ++s) {
     bool lose = false;
-    const int vi = lane + 64 * s;
-    if ((tied >> s) & 1u) {
-      const BallOff o = ball_off(fa.ball, vi);
-      const int z = iz + o.dz, x = ix + o.dx, y = iy + o.dy;
-      if (z >= 0 && z < fa.Z && x >= 0 && x < fa.X && y >= 0 && y < fa.Y) {
+    if ((tied >> s) & 1u)
+      sb.voxel(s, [&](int z, int x, int y, bool in) {
+        if (!in) return;
         const double q[3] = {(double)z, (double)x, (double)y};
         KdQueue<IA3_LDS KdQEntry*> queue((IA3_LDS KdQEntry*)&heap[0][lane], 64, qcap);
         const int w = kd_nearest(tree, q, 2.0 * fa.radius, queue);
         overflow |= queue.overflow;
         lose = w != i - seed0;
-      }
-    }
+      });
     const unsigned long long m = __ballot(lose);
     if (lane == 0) tie_lost[(size_t)i * SLOTS + s] = m;
   }
@@ -885,7 +825,7 @@ __device__ __forceinline__ int gather_repeat(const FitArgs& fa, int i, IA3_LDS B
   int vz[SLOTS], vx[SLOTS], vy[SLOTS];
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
-    const int vi = lane + 64 * s;
+    const int vi = ball_vi(lane, s);
     vz[s] = 0; vx[s] = 0; vy[s] = 0; vals[s] = 0.0;
     if (vi < fa.nball) {
       const BallOff o = ball_off(fa.ball, vi);
@@ -927,9 +867,7 @@ __device__ __forceinline__ int gather_repeat(const FitArgs& fa, int i, IA3_LDS B
     bl->cz[s][lane] = (float)vz[s]; bl->cx[s][lane] = (float)vx[s]; bl->cy[s][lane] = (float)vy[s];
   }
   valid_out = valid;
-  return __popcll(__ballot(valid & 1u)) + __popcll(__ballot(valid & 2u)) + __popcll(__ballot(valid & 4u)) +
-         __popcll(__ballot(valid & 8u)) + __popcll(__ballot(valid & 16u)) + __popcll(__ballot(valid & 32u)) +
-         __popcll(__ballot(valid & 64u)) + __popcll(__ballot(valid & 128u));
+  return ball_count(valid);
 }
 
 // ---- one work-list position ------------------------------------------------------------------------------------------
@@ -1281,7 +1219,7 @@ __global__ __launch_bounds__(64, 2) void fit_voxels_k(VoxArgs va, int n_fits, do
     double vals[SLOTS];
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s) {
-      const int vi = lane + 64 * s;
+      const int vi = ball_vi(lane, s);
       float fz = 0.f, fx = 0.f, fy = 0.f;
       vals[s] = 0.0;
       if (vi < n) {
@@ -1392,16 +1330,7 @@ struct ia3_fitter {
 
 namespace {
 
-int build_ball(int r, std::vector<signed char>& ball) {
-  ball.clear();
-  for (int z = -r; z < r; ++z)
-    for (int x = -r; x < r; ++x)
-      for (int y = -r; y < r; ++y)
-        if (z * z + x * x + y * y <= r * r) { ball.push_back((signed char)z); ball.push_back((signed char)x); ball.push_back((signed char)y); ball.push_back(0); }
-  return (int)(ball.size() / 4);
-}
-
-int g_nb_cap = MAXNB;   // IA3_TUNE_FIT_NBLIST
+int g_nb_cap = BALL_NBLIST;   // IA3_TUNE_FIT_NBLIST
 int g_fit_fuse = 1;     // IA3_TUNE_FIT_FUSE: 1 = a seed without neighbours gets its first fit and sweep 1 from one wave
 int g_fit_maxfev = 0;   // IA3_DEBUG_FIT_MAXFEV: profiling only (splits the kernel time into a fixed and a per-evaluation part)
 int g_fit_waves = 2;    // IA3_TUNE_FIT_WAVES: persistent waves per SIMD (the kernel's 256 registers allow two)
@@ -1459,21 +1388,21 @@ void ia3_fit_destroy(ia3_fitter* f) {
 }
 
 // The ball offset table depends on the radius only: uploaded once per process and radius, kept for good.
-static int ball_table(int radius, const signed char** d_ball, int* nball) {
+static int ball_table(int radius, const int** d_ball, int* nball) {
   struct Entry { pid_t pid; int radius, nball; void* d; };
   static std::vector<Entry> cache;
   static std::mutex mu;
   std::lock_guard<std::mutex> lk(mu);
   for (auto& e : cache)
-    if (e.pid == getpid() && e.radius == radius) { *d_ball = (const signed char*)e.d; *nball = e.nball; return IA3_OK; }
-  std::vector<signed char> ball;
-  const int nb = build_ball(radius, ball);
+    if (e.pid == getpid() && e.radius == radius) { *d_ball = (const int*)e.d; *nball = e.nball; return IA3_OK; }
+  std::vector<int> ball;
+  const int nb = ball_build(radius, ball);
   if (nb > MAXBALL) return set_error(IA3_EUNSUPPORTED, "radius_fit %d gives %d voxels (> %d)", radius, nb, MAXBALL);
   void* d = nullptr;
-  IA3_HIP(hipMalloc(&d, ball.size()));
-  IA3_HIP(hipMemcpy(d, ball.data(), ball.size(), hipMemcpyHostToDevice));
+  IA3_HIP(hipMalloc(&d, ball.size() * sizeof(int)));
+  IA3_HIP(hipMemcpy(d, ball.data(), ball.size() * sizeof(int), hipMemcpyHostToDevice));
   cache.push_back(Entry{getpid(), radius, nb, d});
-  *d_ball = (const signed char*)d; *nball = nb;
+  *d_ball = (const int*)d; *nball = nb;
   return IA3_OK;
 }
 
@@ -1500,7 +1429,7 @@ static int fit_create_impl(const FovSeeds* fovs, int n_fov, const ia3_fit_params
   if (ntot > 0x3fffffff) return set_error(IA3_EUNSUPPORTED, "too many seeds");
   const int n = (int)ntot;
   const ia3_stack* im = fovs[0].im;
-  const signed char* d_ball = nullptr;
+  const int* d_ball = nullptr;
   int nball = 0;
   rc = ball_table(p->radius_fit, &d_ball, &nball); if (rc) return rc;
   ia3_fitter* f = new ia3_fitter();   // value-initialised: pointers null, flags false
@@ -1520,7 +1449,7 @@ static int fit_create_impl(const FovSeeds* fovs, int n_fov, const ia3_fit_params
   const size_t b_memo = al(sizeof(unsigned long long) * (size_t)n);
   const size_t zero_bytes = b_state + b_nvox + b_nfev + b_memo + b_conv + b_niter + b_cnt + b_done + b_ctl + b_ovf + b_fties + b_fcnt;
   const size_t b_ps = al(sizeof(float) * 11 * (size_t)n);
-  const size_t b_ncnt = al(sizeof(int) * (size_t)n), b_nidx = al(sizeof(int) * MAXNB * (size_t)n);
+  const size_t b_ncnt = al(sizeof(int) * (size_t)n), b_nidx = al(sizeof(int) * BALL_NBLIST * (size_t)n);
   const size_t b_tflag = al(sizeof(int) * (size_t)n), b_tlost = al(sizeof(unsigned long long) * SLOTS * (size_t)n);
   f->pool_bytes = up_bytes + zero_bytes + b_ps + b_ncnt + b_nidx + b_tflag + b_tlost;
   f->pool = ws_get(f->pool_bytes);
@@ -1611,7 +1540,7 @@ static int fit_create_impl(const FovSeeds* fovs, int n_fov, const ia3_fit_params
     const double rr = 2.0 * p->radius_fit;
     ProfScope ps("nbr_build");
     hipLaunchKernelGGL(nbr_build_k, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, st, (const double*)f->d_seeds, n, rr * rr,
-                       (int*)f->d_nbr_cnt, (int*)f->d_nbr_idx, (int*)f->d_nbr_overflow, (const int*)d_ball, nball,
+                       (int*)f->d_nbr_cnt, (int*)f->d_nbr_idx, (int*)f->d_nbr_overflow, d_ball, nball,
                        im->Z, im->X, im->Y, (int*)f->d_tie_flag, &((StageCtl*)f->d_ctl)->ties,
                        (const int*)f->d_fov_of, (const int*)f->d_fov_start, (int*)f->d_fov_ties,
                        (unsigned long long*)f->d_fov_counters);
@@ -1634,7 +1563,7 @@ int ia3_fit_create(const ia3_stack* im, const double* centers_zxy, int n, const 
 }  // extern "C"
 
 namespace ia3k {
-void set_fit_nblist(int cap) { g_nb_cap = cap < 0 ? 0 : (cap > MAXNB ? MAXNB : cap); }
+void set_fit_nblist(int cap) { g_nb_cap = cap < 0 ? 0 : (cap > BALL_NBLIST ? BALL_NBLIST : cap); }
 int get_fit_nblist() { return g_nb_cap; }   // fastfit.hip reads its neighbour lists under the same knob
 void set_fit_fuse(int on) { g_fit_fuse = on ? 1 : 0; }
 void set_fit_maxfev(int n) { g_fit_maxfev = n; }
@@ -1881,18 +1810,18 @@ static int resolve_ties_host(ia3_fitter* f) {
     for (int i = s0; i < s0 + nk; ++i) {
       if (!flag[(size_t)i]) continue;
       const double* c0 = f->host_seeds.data() + 3 * (size_t)i;
-      const int iz = (int)c0[0], ix = (int)c0[1], iy = (int)c0[2];
+      const SeedBall sb{ball.data(), f->nball, (int)c0[0], (int)c0[1], (int)c0[2], im->Z, im->X, im->Y};
       for (int vi = 0; vi < f->nball; ++vi) {
-        const int w_ = ball[(size_t)vi];
-        const int z = iz + (int)(signed char)(w_ & 0xff), x = ix + (int)(signed char)((w_ >> 8) & 0xff), y = iy + (int)(signed char)((w_ >> 16) & 0xff);
-        if (z < 0 || z >= im->Z || x < 0 || x >= im->X || y < 0 || y >= im->Y) continue;
-        const double q[3] = {(double)z, (double)x, (double)y};
+        double q[3];
+        bool inside = false;
+        sb.at(vi, [&](int z, int x, int y, bool in) { q[0] = (double)z; q[1] = (double)x; q[2] = (double)y; inside = in; });
+        if (!inside) continue;
         KdQueue<KdQEntry*> queue(heap.data(), 1, (int)heap.size());
         const int w = kd_nearest(t, q, r2x, queue);
         if (queue.overflow) return set_error(IA3_EUNSUPPORTED, "Voronoi tie query exceeded the host queue");
         if (w < 0 || w == i - s0) continue;
         const double* cw = f->host_seeds.data() + 3 * (size_t)(s0 + w);
-        if (d2(cw, q[0], q[1], q[2]) == d2(c0, q[0], q[1], q[2])) lost[(size_t)i * SLOTS + (size_t)(vi / 64)] |= 1ull << (vi % 64);
+        if (d2(cw, q[0], q[1], q[2]) == d2(c0, q[0], q[1], q[2])) lost[(size_t)i * SLOTS + (size_t)ball_slot(vi)] |= 1ull << ball_lane(vi);
       }
     }
   }
@@ -2035,7 +1964,7 @@ int ia3_fit_results_ex(ia3_fitter* f, float* ps, uint8_t* success, int* nvox, in
     if (rows) memcpy(ps, hb.data() + head, rows);
   }
   { const int rc_ = check_ctl(hc); if (rc_) return rc_; }
-  (void)ovf;   // > MAXNB neighbours somewhere: those seeds scanned the seed list instead (each_neighbour); not an error
+  (void)ovf;   // > BALL_NBLIST neighbours somewhere: those seeds scanned the seed list instead (each_neighbour); not an error
   if (success) for (int i = 0; i < f->n; ++i) success[i] = (uint8_t)stv[i].success;
   return IA3_OK;
 }
@@ -2166,14 +2095,10 @@ __device__ __attribute__((noinline)) double view_f0(const Geom* g, int z, int x,
 __device__ __forceinline__ void view_geom_of(const FitArgs& fa, int j, Geom* g) {
   view_geom(&fa.state[j], fa.seeds + 3 * (size_t)j, fa.min_ws, fa.max_ws, fa.init_w, fa.variant, g);
 }
-// the ball test of gather_repeat: offsets in [-r, r) on every axis, inside the sphere
-__device__ __forceinline__ bool view_in_ball(int oz, int ox, int oy, int r) {
-  return oz >= -r && oz < r && ox >= -r && ox < r && oy >= -r && oy < r && oz * oz + ox * ox + oy * oy <= r * r;
-}
 
 // gparms: the voxels of every seed's first fit (gather_first decides, so membership is the fit's own), packed to the
-// front in ball order — the place of ball voxel lane + 64 * slot is its rank among the valid ones (ballot + the count of
-// lower lanes, slot by slot).  zxy: n x nball x 3, val: n x nball (image values, exact in float64), cnt: n.
+// front in ball order — the place of a ball voxel is its rank among the valid ones (ballot + the count of lower lanes,
+// slot by slot).  zxy: n x nball x 3, val: n x nball (image values, exact in float64), cnt: n.
 __global__ __launch_bounds__(64) void view_voxels_k(FitArgs fa, int* __restrict__ cnt, int* __restrict__ zxy,
                                                     double* __restrict__ val) {
   __shared__ BallLds bls;
@@ -2181,18 +2106,18 @@ __global__ __launch_bounds__(64) void view_voxels_k(FitArgs fa, int* __restrict_
   unsigned valid = 0;
   double vals[SLOTS];
   gather_first(fa, i, (IA3_LDS BallLds*)&bls, valid, vals);
-  const int iz = (int)fa.seeds[3 * i], ix = (int)fa.seeds[3 * i + 1], iy = (int)fa.seeds[3 * i + 2];
+  const SeedBall sb = seed_ball(fa, i);
   int base = 0;
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
     const bool ok = (valid >> s) & 1u;
     const unsigned long long m = __ballot(ok);
-    if (ok) {
-      const BallOff o = ball_off(fa.ball, lane + 64 * s);
-      const size_t q = (size_t)i * fa.nball + (size_t)(base + __popcll(m & ((1ull << lane) - 1ull)));
-      zxy[3 * q] = iz + o.dz; zxy[3 * q + 1] = ix + o.dx; zxy[3 * q + 2] = iy + o.dy;
-      val[q] = vals[s];
-    }
+    if (ok)
+      sb.voxel(s, [&](int z, int x, int y, bool) {
+        const size_t q = (size_t)i * fa.nball + (size_t)(base + lane_rank(m));
+        zxy[3 * q] = z; zxy[3 * q + 1] = x; zxy[3 * q + 2] = y;
+        val[q] = vals[s];
+      });
     base += __popcll(m);
   }
   if (lane == 0) cnt[i] = base;
@@ -2209,20 +2134,15 @@ __global__ __launch_bounds__(64) void view_recs_k(FitArgs fa, int* __restrict__ 
   if (x11 && lane < NP + 1) x11[(size_t)i * (NP + 1) + lane] = lane < NP ? si->x[lane] : si->delta;
   Geom g;
   if (hr) view_geom_of(fa, i, &g);
-  const int iz = (int)fa.seeds[3 * i], ix = (int)fa.seeds[3 * i + 1], iy = (int)fa.seeds[3 * i + 2];
+  const SeedBall sb = seed_ball(fa, i);
   int base = 0;
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
-    const int vi = lane + 64 * s;
     bool ok = false;
     int z = 0, x = 0, y = 0;
-    if (vi < fa.nball) {
-      const BallOff o = ball_off(fa.ball, vi);
-      z = iz + o.dz; x = ix + o.dx; y = iy + o.dy;
-      ok = z >= 0 && z < fa.Z && x >= 0 && x < fa.X && y >= 0 && y < fa.Y;
-    }
+    sb.voxel(s, [&](int vz, int vx, int vy, bool in) { z = vz; x = vx; y = vy; ok = in; });
     const unsigned long long m = __ballot(ok);
-    if (ok && hr) rec[(size_t)i * fa.nball + (size_t)(base + __popcll(m & ((1ull << lane) - 1ull)))] = view_f0(&g, z, x, y);
+    if (ok && hr) rec[(size_t)i * fa.nball + (size_t)(base + lane_rank(m))] = view_f0(&g, z, x, y);
     base += __popcll(m);
   }
   if (lane == 0) { cnt[i] = base; has[i] = hr ? 1 : 0; }
@@ -2239,25 +2159,21 @@ __global__ __launch_bounds__(256) void view_cast_k(const void* __restrict__ im, 
 // followed by the higher ones that hold the voxel.  T = double (im_subtr / im_add) or float (rounded once at the store).
 template <class T>
 __global__ __launch_bounds__(64) void view_resid_k(FitArgs fa, T* __restrict__ out) {
-  const int i = (int)blockIdx.x, lane = threadIdx.x & 63;
+  const int i = (int)blockIdx.x;
   const int r = fa.radius;
-  const int iz = (int)fa.seeds[3 * i], ix = (int)fa.seeds[3 * i + 1], iy = (int)fa.seeds[3 * i + 2];
+  const SeedBall sb = seed_ball(fa, i);
   unsigned own = 0;
   int vz[SLOTS], vx[SLOTS], vy[SLOTS];
   double vals[SLOTS];
 #pragma unroll
   for (int s = 0; s < SLOTS; ++s) {
-    const int vi = lane + 64 * s;
     vz[s] = 0; vx[s] = 0; vy[s] = 0; vals[s] = 0.0;
-    if (vi < fa.nball) {
-      const BallOff o = ball_off(fa.ball, vi);
-      const int z = iz + o.dz, x = ix + o.dx, y = iy + o.dy;
-      if (z >= 0 && z < fa.Z && x >= 0 && x < fa.X && y >= 0 && y < fa.Y) {
-        own |= 1u << s;
-        vals[s] = load_voxel(fa.ims[0], fa.dtype, ((size_t)z * fa.X + x) * fa.Y + y);
-        vz[s] = z; vx[s] = x; vy[s] = y;
-      }
-    }
+    sb.voxel(s, [&](int z, int x, int y, bool in) {
+      if (!in) return;
+      own |= 1u << s;
+      vals[s] = load_voxel(fa.ims[0], fa.dtype, ((size_t)z * fa.X + x) * fa.Y + y);
+      vz[s] = z; vx[s] = x; vy[s] = y;
+    });
   }
   bool self_done = false;
   auto subtract_self = [&]() {
@@ -2274,7 +2190,7 @@ __global__ __launch_bounds__(64) void view_resid_k(FitArgs fa, T* __restrict__ o
     if (j < i) {
 #pragma unroll
       for (int s = 0; s < SLOTS; ++s)
-        if ((own & (1u << s)) && view_in_ball(vz[s] - jz, vx[s] - jx, vy[s] - jy, r)) own &= ~(1u << s);
+        if ((own & (1u << s)) && in_ball(vz[s] - jz, vx[s] - jx, vy[s] - jy, r)) own &= ~(1u << s);
       return true;
     }
     if (!self_done) subtract_self();
@@ -2283,7 +2199,7 @@ __global__ __launch_bounds__(64) void view_resid_k(FitArgs fa, T* __restrict__ o
     view_geom_of(fa, j, &gj);
 #pragma unroll
     for (int s = 0; s < SLOTS; ++s)
-      if ((own & (1u << s)) && view_in_ball(vz[s] - jz, vx[s] - jx, vy[s] - jy, r)) vals[s] -= view_f0(&gj, vz[s], vx[s], vy[s]);
+      if ((own & (1u << s)) && in_ball(vz[s] - jz, vx[s] - jx, vy[s] - jy, r)) vals[s] -= view_f0(&gj, vz[s], vx[s], vy[s]);
     return true;
   });
   if (!self_done) subtract_self();

@@ -16,6 +16,7 @@
 // with explicit roundings.  np.log is not evaluated here: a search carries the heap number of the node it ends on and the
 // host supplies the log of that node's mid (ia3.h).
 #include "ia3_rt.h"
+#include "ia3_wave.h"
 #include <math.h>
 #include <string.h>
 #include <rocprim/rocprim.hpp>
@@ -151,22 +152,6 @@ __device__ inline void local_center(const double* __restrict__ ref, int p, int R
   for (int c = 0; c < 3; ++c) out[c] = nm[c].mean();
 }
 
-// Appending to the reference arrays, one global atomic per workgroup and array: every wavefront reserves its share of
-// the workgroup's count in LDS (wave_reserve), the workgroup's total takes a place in the array with one atomic, and the
-// lanes store behind it.  Every lane of the workgroup must take every step.
-struct Slot { int wave_off, rank; };
-__device__ inline Slot wave_reserve(int* s_count, bool ok) {
-  const unsigned long long ballot = __ballot(ok);
-  Slot sl{0, 0};
-  if (!ballot) return sl;
-  const int lane = threadIdx.x & 63, leader = __ffsll((long long)ballot) - 1;
-  int off = 0;
-  if (lane == leader) off = atomicAdd(s_count, __popcll(ballot));
-  sl.wave_off = __shfl(off, leader);
-  sl.rank = __popcll(ballot & ((1ull << lane) - 1ull));
-  return sl;
-}
-
 struct EArgs {
   const double* picks; const double* ref; const double* ctr;
   const int* chan; const int* win_start; const int* win_idx;
@@ -178,6 +163,9 @@ struct EArgs {
   int* cnt;                  // [3][PK_KEYS]
 };
 
+// Appending to the reference arrays, one global atomic per workgroup and array: every wavefront reserves its share of
+// the workgroup's count in LDS (ia3::wave_append), the workgroup's total takes a place in the array with one atomic, and
+// the lanes store behind it.  Every lane of the workgroup must take every step.
 __global__ __launch_bounds__(PK_THREADS) void estep_k(EArgs A) {
   __shared__ int s_count[3 * PK_KEYS], s_base[3 * PK_KEYS];
   const int PR = A.P * A.R;
@@ -200,16 +188,16 @@ __global__ __launch_bounds__(PK_THREADS) void estep_k(EArgs A) {
       for (int k = 0; k < 3; ++k) A.out[k][e] = v[k];
     }
     __syncthreads();
-    Slot own[3], all[3];   // the lane's places in its channel's array and in 'all', per kind
+    int own[3], all[3];   // the lane's places in its channel's array and in 'all', per kind
     for (int k = 0; k < 3; ++k) {
       const bool ok = live && v[k] == v[k];
-      own[k] = Slot{0, 0};
+      own[k] = 0;
       if (A.split)
         for (int c = 0; c < A.nch; ++c) {
-          const Slot sl = wave_reserve(s_count + k * PK_KEYS + c, ok && ch == c);
+          const int sl = ia3::wave_append(s_count + k * PK_KEYS + c, ok && ch == c);
           if (ch == c) own[k] = sl;
         }
-      all[k] = wave_reserve(s_count + k * PK_KEYS + A.nch, ok);
+      all[k] = ia3::wave_append(s_count + k * PK_KEYS + A.nch, ok);
     }
     __syncthreads();
     if (threadIdx.x < 3 * PK_KEYS && s_count[threadIdx.x] > 0)
@@ -217,8 +205,8 @@ __global__ __launch_bounds__(PK_THREADS) void estep_k(EArgs A) {
     __syncthreads();
     for (int k = 0; k < 3; ++k) {
       if (!(live && v[k] == v[k])) continue;
-      if (A.split) A.seg[k][A.seg_off[ch] + s_base[k * PK_KEYS + ch] + own[k].wave_off + own[k].rank] = v[k];
-      A.all[k][s_base[k * PK_KEYS + A.nch] + all[k].wave_off + all[k].rank] = v[k];
+      if (A.split) A.seg[k][A.seg_off[ch] + s_base[k * PK_KEYS + ch] + own[k]] = v[k];
+      A.all[k][s_base[k * PK_KEYS + A.nch] + all[k]] = v[k];
     }
     __syncthreads();   // s_count and s_base are reused by the next pass
   }

@@ -11,6 +11,7 @@
 // compiled without FMA contraction); a later candidate wins only when its ROOT is smaller, and the first NaN of a row
 // wins it, as np.argmin has it.  Counts are int32 atomics: every result is the same on every run.
 #include "ia3_rt.h"
+#include "ia3_wave.h"
 #include <chrono>
 #include <math.h>
 #include <vector>
@@ -182,18 +183,12 @@ __global__ __launch_bounds__(SEL_THREADS) void gather_k(const int* __restrict__ 
                                                          Ctl* __restrict__ ctl) {
   if (ctl->done) return;
   const int removed = ctl->removed;
-  const int lane = threadIdx.x & 63;
   // n rounded up to whole wavefronts, so that a ballot always has 64 lanes behind it
   const unsigned span = ((unsigned)n + 63u) & ~63u;
   for (unsigned i = blockIdx.x * (unsigned)SEL_THREADS + threadIdx.x; i < span; i += gridDim.x * (unsigned)SEL_THREADS) {
     const bool hit = i < (unsigned)n && owner[i] == removed;
-    const unsigned long long ballot = __ballot(hit);
-    if (ballot) {
-      unsigned basepos = 0;
-      if (lane == 0) basepos = atomicAdd(&ctl->m, (unsigned)__popcll(ballot));
-      basepos = __shfl(basepos, 0);
-      if (hit) list[basepos + (unsigned)__popcll(ballot & ((1ull << lane) - 1ull))] = i;
-    }
+    const unsigned pos = ia3::wave_append(&ctl->m, hit);
+    if (hit) list[pos] = i;
   }
 }
 

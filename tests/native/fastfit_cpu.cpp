@@ -1,8 +1,27 @@
-// TEST INFRASTRUCTURE — host build of the moment fit's arithmetic (csrc/ia3_fastfit.h) and of NumPy's summation order
-// (csrc/ia3_npsum.h), the headers fastfit.hip and fit.hip compile for the device, so both can be compared with NumPy and
-// with the reference's rows on the CPU.  Not shipped, not a fallback.
+// TEST INFRASTRUCTURE — host build of the moment fit's arithmetic (csrc/ia3_fastfit.h), of NumPy's summation order
+// (csrc/ia3_npsum.h) and of the seed ball's table and voxel-to-lane map (csrc/ia3_ball.h), the headers fastfit.hip and
+// fit.hip compile for the device, so they can be compared with NumPy and with the reference's rows on the CPU.  Not
+// shipped, not a fallback.
 #include <vector>
 #include "../../imageanalysis3_amd/csrc/ia3_fastfit.h"
+#include "../../imageanalysis3_amd/csrc/ia3_ball.h"
+
+// the seed ball of radius r: its packed words (at most cap are written); returns the number of voxels
+extern "C" int ia3cpu_ball_table(int r, int* words, int cap) {
+  std::vector<int> ball;
+  const int n = ia3::ball_build(r, ball);
+  for (int k = 0; k < n && k < cap; ++k) words[k] = ball[(size_t)k];
+  return n;
+}
+extern "C" void ia3cpu_ball_off(const int* words, int vi, int* dzxy) {
+  const ia3::BallOff o = ia3::ball_off(words, vi);
+  dzxy[0] = o.dz; dzxy[1] = o.dx; dzxy[2] = o.dy;
+}
+extern "C" int ia3cpu_ball_slot(int vi) { return ia3::ball_slot(vi); }
+extern "C" int ia3cpu_ball_lane(int vi) { return ia3::ball_lane(vi); }
+extern "C" int ia3cpu_ball_vi(int lane, int slot) { return ia3::ball_vi(lane, slot); }
+extern "C" int ia3cpu_in_ball(int oz, int ox, int oy, int r) { return ia3::in_ball(oz, ox, oy, r) ? 1 : 0; }
+extern "C" void ia3cpu_ball_limits(int* out) { out[0] = ia3::BALL_LANES; out[1] = ia3::BALL_SLOTS; out[2] = ia3::BALL_MAXVOX; }
 
 extern "C" float ia3cpu_npsum_f32(const float* a, int n) { return ia3::np_sum<float>(a, n); }
 extern "C" double ia3cpu_npsum_f64(const double* a, int n) { return ia3::np_sum<double>(a, n); }

@@ -33,7 +33,7 @@ SIGNATURES = {
 def native():
     src = os.path.join(HERE, "native", "fastfit_cpu.cpp")
     dep = os.path.join(HERE, "..", "imageanalysis3_amd", "csrc")
-    newest = max(os.path.getmtime(p) for p in (src, os.path.join(dep, "ia3_fastfit.h"), os.path.join(dep, "ia3_npsum.h")))
+    newest = max(os.path.getmtime(p) for p in [src] + [os.path.join(dep, h) for h in ("ia3_fastfit.h", "ia3_npsum.h", "ia3_ball.h")])
     if not os.path.isfile(SO) or os.path.getmtime(SO) < newest:
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", SO, src])
     lib = C.CDLL(SO)
@@ -158,6 +158,42 @@ def test_voronoi_header_equals_statement(native, gold):
                                    off.ctypes.data_as(C.c_void_p), len(off), own.ctypes.data_as(C.c_void_p))
             assert np.array_equal(own.astype(bool), want), i
     assert ties > 100
+
+
+def test_ball_header_equals_numpy(native):
+    """csrc/ia3_ball.h for every supported radius: the table is NumPy's ball in NumPy's order, its packed words unpack to
+    the same offsets, voxel index and (slot, lane) round-trip (r = 2, 3, 4 end in a partly filled slot) and in_ball is
+    membership in the table."""
+    lim = (C.c_int * 3)()
+    native.ia3cpu_ball_limits(lim)
+    lanes, slots, maxvox = lim
+    assert (lanes, slots, maxvox) == (64, 8, 512)
+    partly = []
+    for r in range(1, 6):
+        off = np.reshape(np.indices((2 * r,) * 3) - r, (3, -1)).T
+        want = off[(off * off).sum(1) <= r * r]
+        words = np.zeros(maxvox, dtype=np.int32)
+        n = native.ia3cpu_ball_table(r, words.ctypes.data_as(C.c_void_p), maxvox)
+        assert n == len(want) <= maxvox, r
+        got = np.zeros((n, 3), dtype=np.int32)
+        for vi in range(n):
+            native.ia3cpu_ball_off(words.ctypes.data_as(C.c_void_p), vi, got[vi].ctypes.data_as(C.c_void_p))
+        assert np.array_equal(got, want), r
+        assert np.array_equal(words[:n], (want[:, 0] & 0xff) | ((want[:, 1] & 0xff) << 8) | ((want[:, 2] & 0xff) << 16)), r
+        seen = set()
+        for vi in range(n):
+            s, l = native.ia3cpu_ball_slot(vi), native.ia3cpu_ball_lane(vi)
+            assert 0 <= s < slots and 0 <= l < lanes and native.ia3cpu_ball_vi(l, s) == vi, (r, vi)
+            seen.add((s, l))
+        assert len(seen) == n
+        if n % lanes:
+            partly.append(r)
+            last = native.ia3cpu_ball_slot(n - 1)
+            assert sum(s == last for s, _ in seen) == n % lanes
+        member = set(map(tuple, want))
+        for o in np.reshape(np.indices((2 * r + 3,) * 3) - (r + 1), (3, -1)).T:
+            assert bool(native.ia3cpu_in_ball(int(o[0]), int(o[1]), int(o[2]), r)) == (tuple(o) in member), (r, o)
+    assert {2, 3, 4} <= set(partly)
 
 
 def test_seed_statement_equals_reference(gold):

@@ -42,9 +42,9 @@ MEASURED_ORACLE = {"edge_f32": 2.48e-15, "clu_f32": 4.82e-15, "c1_u16": 4.83e-15
 ORACLE_BAR = min(1e-4, 4 * max(MEASURED_ORACLE.values()))
 
 
-def _fitter(im, seeds, cls=None, **kw):
+def _fitter(im, seeds, cls=None, radius=RADIUS, **kw):
     from imageanalysis3_amd.External.Fitting_v4 import iter_fit_seed_points
-    return (cls or iter_fit_seed_points)(im, np.asarray(seeds).T, radius_fit=RADIUS, **kw)
+    return (cls or iter_fit_seed_points)(im, np.asarray(seeds).T, radius_fit=radius, **kw)
 
 
 def _host_model(x11, seed, X, min_w=0.5, max_w=4.):
@@ -99,6 +99,27 @@ def test_voxel_sets_equal_oracle(name):
         diff = sum(not np.array_equal(np.asarray(a[1]), b[1]) for a, b in zip(
             _lowest_index_cells(fo, im.shape), g))
         assert diff >= 1
+
+
+@pytest.mark.parametrize("radius", [2, 3])
+def test_voxel_sets_equal_oracle_partly_filled_slot(radius):
+    """test_voxel_sets_equal_oracle's geometry at the radii whose ball ends inside a slot (30 and 120 voxels: slot 0 and
+    slot 1 partly filled) on the clustered fixture, where seeds lie within 2r of each other at both radii (the oracle alone
+    cuts 1 and 10 cells): voxel sets, their values and the first fit's voxel counts, exactly.  No fitted row is compared."""
+    name = "clu_f32"
+    im, seeds, _, fo = VR.oracle_fit(name, radius)
+    whole = [VR.ball_voxels(c, radius, im.shape).shape[1] for c in seeds]
+    assert len(VR.ball_offsets(radius)[0]) % 64 != 0
+    assert sum(oX.shape[1] < n for (_, oX, _), n in zip(fo.gparms, whole)) >= 1     # the neighbour path is exercised
+    f = _fitter(im, seeds, radius=radius)
+    f.firstfit()
+    nvox = np.array(f.nvox)
+    g = f.gparms
+    assert len(g) == len(seeds) == len(fo.gparms) == len(nvox)
+    for i, ((im_, X, _), (oim, oX, _)) in enumerate(zip(g, fo.gparms)):
+        assert nvox[i] == oX.shape[1], i
+        assert X.dtype == np.int64 and X.shape == (3, nvox[i]) and np.array_equal(X, oX), i
+        assert im_.dtype == im.dtype and im_.tobytes() == np.ascontiguousarray(oim).tobytes(), i
 
 
 def _lowest_index_cells(fo, shape):
