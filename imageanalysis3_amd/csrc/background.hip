@@ -265,7 +265,9 @@ int ia3_find_background_dev(const ia3_stack* im, const double* edges, int n_edge
   double res[2];
   IA3_HIP(hipMemcpyAsync(res, dres.p, sizeof(res), hipMemcpyDeviceToHost, st));
   IA3_HIP(hipStreamSynchronize(st));
-  if (res[1] != 0) {   // no histogram peak: np.nanmedian(im)
+  // no histogram peak: np.nanmedian(im) of a stack without NaN.  stack_median_all is np.median: NaN for a float32 stack
+  // that holds one, not the median of the rest
+  if (res[1] != 0) {
     float m = 0;
     rc = ia3k::stack_median_all(im, &m); if (rc) return rc;
     res[0] = (double)m;

@@ -3,7 +3,7 @@
 // the unwarped ones shifted by their rounded drift and filled up with their whole-stack median.
 //   chrom_add_k     up to 16 stacks into the float64 volume in one launch: each thread owns 8 consecutive y voxels of one
 //                   (z, x) row, reads them from every image and does one read-modify-write of its 64 bytes
-//   ia3_select.h    np.median of a stack (the radix select morph.hip uses for its plane medians)
+//   ia3_select.h    np.median of a stack (the radix select that corrections.hip, stats.hip and morph.hip use as well)
 // Every term and every partial sum is a multiple of 0.5 far below 2^52: the sums are exact, whatever the order of the
 // images and of the operations, and the same on every run.  No atomics, no LDS.
 #include "ia3_rt.h"
@@ -186,7 +186,7 @@ int ia3_stack_median_dev(const ia3_stack* s, double* out) {
   if (s->dtype != IA3_U16 && s->dtype != IA3_F32) return set_error(IA3_EINVAL, "stack dtype must be uint16 or float32");
   if (s->Z < 1 || s->X < 1 || s->Y < 1) return set_error(IA3_EINVAL, "empty stack");
   std::vector<double> med;
-  rc = segment_medians(s->d, s->dtype, 1, (size_t)s->Z * s->X * s->Y, med); if (rc) return rc;
+  rc = host_medians("morph_select", s->d, s->dtype, 1, (size_t)s->Z * s->X * s->Y, med); if (rc) return rc;
   *out = med[0];
   return IA3_OK;
 }
@@ -214,7 +214,7 @@ int ia3_chrom_image_add_dev(ia3_chrom_image* h, const ia3_stack* const* ims, con
   for (int k = 0; k < n; ++k) {
     if (flags[k] == 2) continue;
     std::vector<double> med;
-    rc = segment_medians(ims[k]->d, IA3_U16, 1, h->n, med); if (rc) return rc;
+    rc = host_medians("morph_select", ims[k]->d, IA3_U16, 1, h->n, med); if (rc) return rc;
     bg[k] = med[0];
   }
   if (backgrounds_out)

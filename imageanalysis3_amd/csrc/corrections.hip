@@ -4,11 +4,10 @@
 //   illumination  io_tools/load.py:373-384 out = u16( f32(im) / P[ch] )                        (P (X,Y) f32|f64)
 // NumPy semantics kept: products/quotients are float32 when the profile is float32 and float64 when it is
 // float64; sums run in channel order; float -> uint16 is C truncation (out-of-range values wrap as on x86).
-// All three are single-pass HBM-bound streams; the medians use a 3-pass radix select (11+11+10 bits of the
-// order-preserving uint32 key of the float32 value), batched over the Z planes plus the whole stack, for the
-// two middle ranks NumPy averages.
+// All three are single-pass HBM-bound streams; the medians come from one radix select (ia3_select.h) over the Z planes
+// plus the whole stack, for the two middle ranks NumPy averages, and stay on the device.
 #include "ia3_rt.h"
-#include "ia3_key.h"
+#include "ia3_select.h"
 #include <math.h>
 #include <vector>
 
@@ -21,71 +20,6 @@ __device__ __forceinline__ uint16_t to_u16(double t) {   // numpy .astype(np.uin
   return (uint16_t)(int)t;
 }
 template <class T> __device__ __forceinline__ float ldf(const T* p, size_t i) { return (float)p[i]; }
-
-using ia3key::fkey;       // order-preserving key (ia3_key.h)
-using ia3key::fkey_inv;
-
-constexpr int RB = 2048;  // buckets per pass (11 bits; last pass uses 10)
-struct SelState {         // per problem (plane z or whole stack) and rank r
-  uint32_t prefix;        // key bits decided so far (high bits)
-  unsigned long long k;   // remaining rank inside the current prefix group
-};
-
-// pass p: histogram of the next digit among voxels whose decided high bits match the problem's prefix.
-// problems: index 2*z + r for planes, 2*Z + r for the whole stack.
-template <class T>
-__global__ __launch_bounds__(256) void select_hist_k(const T* __restrict__ im, int Z, size_t plane, int pass,
-                                                     const SelState* __restrict__ st, unsigned int* __restrict__ hist) {
-  __shared__ unsigned int h[4][RB];
-  const int z = blockIdx.y;
-  for (int i = threadIdx.x; i < 4 * RB; i += 256) (&h[0][0])[i] = 0;
-  __syncthreads();
-  const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
-  const uint32_t dmask = pass == 2 ? 0x3ffu : 0x7ffu;
-  const int hi_shift = pass == 0 ? 32 : (pass == 1 ? 21 : 10);
-  uint32_t pre[4];
-  pre[0] = st[2 * z].prefix; pre[1] = st[2 * z + 1].prefix; pre[2] = st[2 * Z].prefix; pre[3] = st[2 * Z + 1].prefix;
-  for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < plane; i += (size_t)gridDim.x * 256) {
-    const uint32_t key = fkey(ldf(im, (size_t)z * plane + i));
-    const uint32_t d = (key >> shift) & dmask;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      bool match = hi_shift >= 32 ? true : ((key >> hi_shift) == (pre[q] >> hi_shift));
-      if (match) atomicAdd(&h[q][d], 1u);
-    }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < RB; i += 256) {
-    if (h[0][i]) atomicAdd(&hist[((size_t)(2 * z) * RB) + i], h[0][i]);
-    if (h[1][i]) atomicAdd(&hist[((size_t)(2 * z + 1) * RB) + i], h[1][i]);
-    if (h[2][i]) atomicAdd(&hist[((size_t)(2 * Z) * RB) + i], h[2][i]);
-    if (h[3][i]) atomicAdd(&hist[((size_t)(2 * Z + 1) * RB) + i], h[3][i]);
-  }
-}
-// one thread per problem: pick the bucket holding rank k, extend the prefix
-__global__ void select_pick_k(SelState* st, const unsigned int* __restrict__ hist, int n_prob, int pass) {
-  int q = blockIdx.x * 64 + threadIdx.x;
-  if (q >= n_prob) return;
-  const int shift = pass == 0 ? 21 : (pass == 1 ? 10 : 0);
-  const int nb = pass == 2 ? 1024 : RB;
-  unsigned long long k = st[q].k, cum = 0;
-  int b = 0;
-  for (; b < nb; ++b) {
-    unsigned long long c = hist[(size_t)q * RB + b];
-    if (cum + c > k) break;
-    cum += c;
-  }
-  if (b >= nb) b = nb - 1;
-  st[q].prefix |= (uint32_t)b << shift;
-  st[q].k = k - cum;
-}
-// medians[z] (Z planes) and medians[Z] (whole stack): float32 mean of the two middle order statistics
-__global__ void select_finish_k(const SelState* __restrict__ st, int Z, float* __restrict__ med) {
-  int z = blockIdx.x * 64 + threadIdx.x;
-  if (z > Z) return;
-  float a = fkey_inv(st[2 * z].prefix), b = fkey_inv(st[2 * z + 1].prefix);
-  med[z] = (a + b) / 2.0f;
-}
 
 template <class T>
 __global__ __launch_bounds__(256) void zshift_apply_k(const T* __restrict__ im, int Z, size_t plane,
@@ -307,45 +241,26 @@ __global__ __launch_bounds__(256) void bleed_rescale_k(ChanPtrs ch, int C, int a
 
 namespace ia3k {
 
-// med[z] for the Z planes and med[Z] for the whole stack (device array of Z+1 floats): np.median in float32
+// med[z] for the Z planes and med[Z] for the whole stack (device array of Z+1 floats): np.median of the stack as float32
+template <class T>
+int stack_medians_of(const ia3_stack* s, float* dmed) {
+  const size_t plane = (size_t)s->X * s->Y;
+  Select<true> sel(s->Z);
+  if (!sel.ok()) return IA3_ENOMEM;
+  ProfScope ps("zshift_median");
+  int rc = sel.run((const T*)s->d, plane, middle_ranks<T>(plane), middle_ranks<T>(plane * s->Z)); if (rc) return rc;
+  return sel.medians<T, float>(plane, dmed);
+}
 int stack_medians(const ia3_stack* s, float* dmed) {
-  hipStream_t st = stream();
-  const int Z = s->Z;
-  const size_t plane = (size_t)s->X * s->Y, n = plane * Z;
-  const int n_prob = 2 * (Z + 1);
-  Scratch dst((size_t)n_prob * sizeof(SelState)), dh((size_t)n_prob * RB * sizeof(unsigned int));
-  if (!dst.p || !dh.p) return IA3_ENOMEM;
-  std::vector<SelState> hs(n_prob);
-  for (int z = 0; z <= Z; ++z) {
-    const unsigned long long cnt = z < Z ? plane : n;
-    hs[2 * z] = SelState{0u, (cnt - 1) / 2};
-    hs[2 * z + 1] = SelState{0u, cnt / 2};
-  }
-  hipError_t e = hipMemcpyAsync(dst.p, hs.data(), hs.size() * sizeof(SelState), hipMemcpyHostToDevice, st);
-  unsigned gx = (unsigned)((plane + 256 * 16 - 1) / (256 * 16));
-  if (gx < 1) gx = 1;
-  {
-    ProfScope ps("zshift_median");
-    for (int pass = 0; pass < 3 && e == hipSuccess; ++pass) {
-      e = hipMemsetAsync(dh.p, 0, (size_t)n_prob * RB * sizeof(unsigned int), st);
-      if (s->dtype == IA3_F32) hipLaunchKernelGGL((select_hist_k<float>), dim3(gx, Z), dim3(256), 0, st, (const float*)s->d, Z, plane, pass, (const SelState*)dst.p, dh.as<unsigned int>());
-      else hipLaunchKernelGGL((select_hist_k<uint16_t>), dim3(gx, Z), dim3(256), 0, st, (const uint16_t*)s->d, Z, plane, pass, (const SelState*)dst.p, dh.as<unsigned int>());
-      hipLaunchKernelGGL(select_pick_k, dim3((n_prob + 63) / 64), dim3(64), 0, st, dst.as<SelState>(), (const unsigned int*)dh.p, n_prob, pass);
-    }
-    hipLaunchKernelGGL(select_finish_k, dim3((Z + 64) / 64), dim3(64), 0, st, (const SelState*)dst.p, Z, dmed);
-  }
-  if (e == hipSuccess) e = hipGetLastError();
-  // hs is read by the (pageable, hence already staged) H2D copy above; nothing else host-side is pending
-  if (e != hipSuccess) return set_error(IA3_EHIP, "median selection failed: %s", hipGetErrorString(e));
-  return IA3_OK;
+  return s->dtype == IA3_F32 ? stack_medians_of<float>(s, dmed) : stack_medians_of<uint16_t>(s, dmed);
 }
 
+// the whole stack's median alone (background.hip): one segment.  host_medians widens to float64 what is exact in
+// float32: the float32 mean of two float32 values, and the mean of two uint16 values, the same in either arithmetic
 int stack_median_all(const ia3_stack* s, float* med_all) {
-  Scratch dmed((size_t)(s->Z + 1) * sizeof(float));
-  if (!dmed.p) return IA3_ENOMEM;
-  int rc = stack_medians(s, dmed.as<float>()); if (rc) return rc;
-  IA3_HIP(hipMemcpyAsync(med_all, dmed.as<float>() + s->Z, sizeof(float), hipMemcpyDeviceToHost, stream()));
-  IA3_HIP(hipStreamSynchronize(stream()));
+  std::vector<double> med;
+  int rc = host_medians("zshift_median", s->d, s->dtype, 1, (size_t)s->Z * s->X * s->Y, med); if (rc) return rc;
+  *med_all = (float)med[0];
   return IA3_OK;
 }
 

@@ -40,7 +40,7 @@ constexpr int DS_BINS = 1 << DS_DIGIT;
 constexpr int DS_PASSES = 9;
 constexpr u64 DS_TOP = 1ull << 63;
 
-// KeyOf<double>::key (ia3_select.h) of a q that is >= +0 and not NaN: the bit pattern with the sign bit set
+// KeyOf<double>::key (ia3_order.h) of a q that is >= +0 and not NaN: the bit pattern with the sign bit set
 IA3_DS_HD u64 ds_key(double q) {
   u64 b;
   memcpy(&b, &q, 8);

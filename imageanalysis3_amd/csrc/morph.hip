@@ -515,21 +515,24 @@ int range_image(const void* im, int kind, const Dims& d, const std::vector<doubl
   return IA3_OK;
 }
 
-// scipy.stats.scoreatpercentile over all n values: the two neighbouring order statistics weighted in float64, the
-// arithmetic ia3_stack_percentiles_dev states (stats.hip)
+// scipy.stats.scoreatpercentile over all n values: the two neighbouring order statistics weighted in float64
 template <class F>
 int percentile_of(const F* seed, size_t n, double per, double* out) {
-  const double idx = per / 100. * (double)(n - 1);
-  const long long i = (long long)idx;
-  const u64 k0 = (u64)i, k1 = (u64)i + 1 < n ? (u64)i + 1 : (u64)i;
-  std::vector<u64> keys;
-  std::vector<unsigned> nan;
-  int rc = seg_select<F>(seed, 1, n, k0, k1, keys, nan); if (rc) return rc;
-  const double s0 = sizeof(F) == 4 ? (double)key_to_f32(keys[0]) : key_to_f64(keys[0]);
-  const double s1 = sizeof(F) == 4 ? (double)key_to_f32(keys[1]) : key_to_f64(keys[1]);
-  if ((double)i == idx) { *out = s0; return IA3_OK; }
-  const double w0 = (double)(i + 1) - idx, w1 = idx - (double)i;
-  *out = (s0 * w0 + s1 * w1) / (w0 + w1);
+  long long i;
+  double idx;
+  percentile_index(per, (long long)n, &i, &idx);
+  Select<false> sel(1);
+  Scratch dv(2 * sizeof(F));
+  if (!sel.ok() || !dv.p) return set_error(IA3_ENOMEM, "scratch of the order statistics");
+  int rc;
+  {
+    ProfScope ps("morph_select");
+    rc = sel.run(seed, n, SelRanks{{(u64)i, (u64)percentile_next(i, (long long)n)}, 2}); if (rc) return rc;
+    rc = sel.values(dv.as<F>()); if (rc) return rc;
+  }
+  F v[2];
+  rc = fetch(dv.as<F>(), 2, v); if (rc) return rc;
+  *out = percentile_value(idx, i, (double)v[0], (double)v[1]);
   return IA3_OK;
 }
 
@@ -549,7 +552,7 @@ int check_seed_args(int filt_size, double per) {
 int seed_mask_bits(const void* im, int kind, const Dims& d, int filt_size, double per, u64* bits, double* threshold) {
   std::vector<double> med;
   // np.median of every plane as the reference's division sees it (chromosome.py:296), widened to float64
-  int rc = segment_medians(im, kind, d.Z, (size_t)d.X * d.Y, med); if (rc) return rc;
+  int rc = host_medians("morph_select", im, kind, d.Z, (size_t)d.X * d.Y, med); if (rc) return rc;
   for (int z = 0; z < d.Z; ++z)
     if (!(med[z] != 0) || !isfinite(med[z]))
       return set_error(IA3_EINVAL, "plane %d has the median %g: the layer adjustment divides by it", z, med[z]);
@@ -629,7 +632,7 @@ int ia3_plane_medians_dev(const ia3_stack* s, double* out) {
   rc = check_image(s, d); if (rc) return rc;
   if (!out) return set_error(IA3_EINVAL, "null output");
   std::vector<double> med;
-  rc = segment_medians(s->d, s->dtype, d.Z, (size_t)d.X * d.Y, med); if (rc) return rc;
+  rc = host_medians("morph_select", s->d, s->dtype, d.Z, (size_t)d.X * d.Y, med); if (rc) return rc;
   memcpy(out, med.data(), (size_t)d.Z * sizeof(double));
   return IA3_OK;
 }

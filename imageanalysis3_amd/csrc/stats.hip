@@ -5,13 +5,9 @@
 //   gaussian_filter(f64 (X, Y))  NI_Correlate1D's summation order, axis 0 then axis 1
 // Everything is integer selection or float64 arithmetic in a fixed order, so results equal NumPy / SciPy bit for bit.
 //
-// Select: 8 key bits per pass, most significant first (uint16: 2 passes, float32: 4).  Pass 0 makes one histogram of
-// the whole stack; after every pass each rank picks the bucket that holds it and ranks whose decided prefixes agree
-// form a group, so a later pass counts once per distinct prefix (the two ranks around a percentile nearly always share
-// theirs).  Blocks count into LDS with integer atomics and add their histogram to the global one once: integer sums,
-// so the result does not depend on the schedule.  Buckets count in 32 bits (a stack holds < 2^32 voxels), ranks in 64.
+// The select is ia3_select.h's, asked for one segment: the whole stack.
 #include "ia3_rt.h"
-#include "ia3_key.h"
+#include "ia3_select.h"
 #include "ia3_gauss_dev.h"
 #include <math.h>
 #include <vector>
@@ -20,121 +16,7 @@ using namespace ia3rt;
 
 namespace {
 
-constexpr int MAXR = 16;      // ranks per call
-constexpr int NB = 256;       // buckets per pass
-constexpr int MAXPASS = 4;
 constexpr int GAUSS_MAX_RADIUS = 1024;
-
-struct SelState {
-  unsigned long long k[MAXR];   // remaining rank inside the rank's prefix group
-  uint32_t prefix[MAXR];        // key bits decided so far (high bits)
-  uint32_t gprefix[MAXR];       // distinct prefixes
-  int grp[MAXR];                // rank -> index into gprefix
-  int ngrp, n;
-};
-struct Ranks { unsigned long long k[MAXR]; };
-
-template <class T> struct KeyOf;
-template <> struct KeyOf<uint16_t> {
-  static constexpr int BITS = 16;
-  static __device__ __forceinline__ uint32_t key(uint16_t v) { return v; }
-  static __device__ __forceinline__ uint16_t inv(uint32_t k) { return (uint16_t)k; }
-};
-template <> struct KeyOf<float> {
-  static constexpr int BITS = 32;
-  // NaNs of either sign order last, as np.sort puts them
-  static __device__ __forceinline__ uint32_t key(float v) { return v != v ? 0xFFFFFFFFu : ia3key::fkey(v); }
-  static __device__ __forceinline__ float inv(uint32_t k) { return ia3key::fkey_inv(k); }
-};
-
-__global__ void sel_init_k(SelState* st, Ranks r, int n) {
-  if (threadIdx.x != 0) return;
-  for (int i = 0; i < MAXR; ++i) {
-    st->k[i] = i < n ? r.k[i] : 0;
-    st->prefix[i] = 0; st->gprefix[i] = 0; st->grp[i] = 0;
-  }
-  st->ngrp = 1; st->n = n;
-}
-
-template <class T>
-__device__ __forceinline__ void sel_count(T v, int pass, int shift, int ngrp, const uint32_t* gp, unsigned int* h) {
-  const uint32_t key = KeyOf<T>::key(v);
-  const uint32_t d = (key >> shift) & (NB - 1);
-  if (pass == 0) { atomicAdd(&h[d], 1u); return; }
-  const uint32_t hi = key >> (shift + 8);
-  for (int g = 0; g < ngrp; ++g)
-    if (hi == gp[g]) atomicAdd(&h[g * NB + d], 1u);
-}
-
-// histogram of the digit of pass `pass` among the voxels that match a group's prefix; 16-byte loads over the aligned body
-template <class T>
-__global__ __launch_bounds__(256) void sel_hist_k(const T* __restrict__ im, size_t n, int pass,
-                                                  const SelState* __restrict__ st, unsigned int* __restrict__ hist) {
-  __shared__ unsigned int h[MAXR * NB];
-  __shared__ uint32_t gp[MAXR];
-  constexpr int V = 16 / sizeof(T);
-  const int shift = KeyOf<T>::BITS - 8 * (pass + 1);
-  const int ngrp = pass == 0 ? 1 : st->ngrp;
-  for (int i = threadIdx.x; i < ngrp * NB; i += 256) h[i] = 0;
-  if (threadIdx.x < MAXR) gp[threadIdx.x] = pass == 0 ? 0u : (st->gprefix[threadIdx.x] >> (shift + 8));
-  __syncthreads();
-  // elements before the first 16-byte boundary and after the last whole vector go one by one (block 0)
-  size_t head = ((16 - ((uintptr_t)im & 15)) & 15) / sizeof(T);
-  if (head > n) head = n;
-  const size_t nvec = (n - head) / V, tail0 = head + nvec * V;
-  if (blockIdx.x == 0) {
-    for (size_t i = threadIdx.x; i < head; i += 256) sel_count<T>(im[i], pass, shift, ngrp, gp, h);
-    for (size_t i = tail0 + threadIdx.x; i < n; i += 256) sel_count<T>(im[i], pass, shift, ngrp, gp, h);
-  }
-  const uint4* body = (const uint4*)(im + head);
-  for (size_t v = (size_t)blockIdx.x * 256 + threadIdx.x; v < nvec; v += (size_t)gridDim.x * 256) {
-    const uint4 q = body[v];
-    T e[V];
-    __builtin_memcpy(e, &q, 16);
-#pragma unroll
-    for (int j = 0; j < V; ++j) sel_count<T>(e[j], pass, shift, ngrp, gp, h);
-  }
-  __syncthreads();
-  unsigned int* out = hist + (size_t)pass * MAXR * NB;
-  for (int i = threadIdx.x; i < ngrp * NB; i += 256)
-    if (h[i]) atomicAdd(&out[i], h[i]);
-}
-
-// one thread per rank picks the bucket that holds it; then the distinct prefixes are listed again
-__global__ void sel_pick_k(SelState* st, const unsigned int* __restrict__ hist, int pass, int bits) {
-  const int r = threadIdx.x, n = st->n;
-  const int shift = bits - 8 * (pass + 1);
-  if (r < n) {
-    const unsigned int* h = hist + (size_t)pass * MAXR * NB + (size_t)st->grp[r] * NB;
-    unsigned long long k = st->k[r], cum = 0;
-    int b = 0;
-    for (; b < NB; ++b) {
-      const unsigned long long c = h[b];
-      if (cum + c > k) break;
-      cum += c;
-    }
-    if (b >= NB) b = NB - 1;
-    st->prefix[r] |= (uint32_t)b << shift;
-    st->k[r] = k - cum;
-  }
-  __syncthreads();
-  if (r == 0) {
-    int ng = 0;
-    for (int i = 0; i < n; ++i) {
-      int g = -1;
-      for (int j = 0; j < ng; ++j) if (st->gprefix[j] == st->prefix[i]) { g = j; break; }
-      if (g < 0) { g = ng++; st->gprefix[g] = st->prefix[i]; }
-      st->grp[i] = g;
-    }
-    st->ngrp = ng;
-  }
-}
-
-template <class T>
-__global__ void sel_finish_k(const SelState* __restrict__ st, T* __restrict__ out) {
-  const int r = threadIdx.x;
-  if (r < st->n) out[r] = KeyOf<T>::inv(st->prefix[r]);
-}
 
 // ---- sum over z of the (clamped) float64 voxels -----------------------------------------------------------------
 template <class T> struct VecOf;
@@ -211,32 +93,19 @@ int check_stack(const ia3_stack* s) {
 
 // the n order statistics, left in `dout` (n values of the stack dtype, device)
 int order_stats(const ia3_stack* s, const long long* ranks, int n, void* dout) {
-  hipStream_t st = stream();
   const size_t nvox = (size_t)s->Z * s->X * s->Y;
-  Ranks r{};
-  for (int i = 0; i < n; ++i) r.k[i] = (unsigned long long)ranks[i];
-  const size_t hist_bytes = (size_t)MAXPASS * MAXR * NB * sizeof(unsigned int);
-  Scratch dst(sizeof(SelState)), dh(hist_bytes);
-  if (!dst.p || !dh.p) return IA3_ENOMEM;
-  const bool f32 = s->dtype == IA3_F32;
-  const int bits = f32 ? 32 : 16, passes = bits / 8;
-  const size_t per_block = 256 * 64;   // voxels a block counts before it adds its histogram to the global one
-  unsigned gx = (unsigned)((nvox + per_block - 1) / per_block);
-  const unsigned gmax = (unsigned)num_cus() * 8;
-  if (gx > gmax) gx = gmax;
-  if (gx < 1) gx = 1;
+  SelRanks r{};
+  for (int i = 0; i < n; ++i) r.k[i] = (u64)ranks[i];
+  r.n = n;
+  Select<false> sel(1);
+  if (!sel.ok()) return IA3_ENOMEM;
   ProfScope ps("order_stats");
-  IA3_HIP(hipMemsetAsync(dh.p, 0, hist_bytes, st));
-  hipLaunchKernelGGL(sel_init_k, dim3(1), dim3(64), 0, st, dst.as<SelState>(), r, n);
-  for (int pass = 0; pass < passes; ++pass) {
-    if (f32) hipLaunchKernelGGL((sel_hist_k<float>), dim3(gx), dim3(256), 0, st, (const float*)s->d, nvox, pass, (const SelState*)dst.p, dh.as<unsigned int>());
-    else hipLaunchKernelGGL((sel_hist_k<uint16_t>), dim3(gx), dim3(256), 0, st, (const uint16_t*)s->d, nvox, pass, (const SelState*)dst.p, dh.as<unsigned int>());
-    hipLaunchKernelGGL(sel_pick_k, dim3(1), dim3(64), 0, st, dst.as<SelState>(), (const unsigned int*)dh.p, pass, bits);
+  if (s->dtype == IA3_F32) {
+    int rc = sel.run((const float*)s->d, nvox, r); if (rc) return rc;
+    return sel.values((float*)dout);
   }
-  if (f32) hipLaunchKernelGGL((sel_finish_k<float>), dim3(1), dim3(64), 0, st, (const SelState*)dst.p, (float*)dout);
-  else hipLaunchKernelGGL((sel_finish_k<uint16_t>), dim3(1), dim3(64), 0, st, (const SelState*)dst.p, (uint16_t*)dout);
-  IA3_KCHECK();
-  return IA3_OK;
+  int rc = sel.run((const uint16_t*)s->d, nvox, r); if (rc) return rc;
+  return sel.values((uint16_t*)dout);
 }
 
 int check_ranks(const ia3_stack* s, const long long* ranks, int n) {
@@ -252,9 +121,7 @@ int order_stats_host(const ia3_stack* s, const long long* ranks, int n, void* ou
   Scratch dout(MAXR * sizeof(float));
   if (!dout.p) return IA3_ENOMEM;
   int rc = order_stats(s, ranks, n, dout.p); if (rc) return rc;
-  IA3_HIP(hipMemcpyAsync(out, dout.p, (size_t)n * esize(s->dtype), hipMemcpyDeviceToHost, stream()));
-  IA3_HIP(hipStreamSynchronize(stream()));
-  return IA3_OK;
+  return fetch(dout.as<char>(), (size_t)n * esize(s->dtype), (char*)out);
 }
 
 int clip_sum_z(const ia3_stack* s, int clip, double lo, double hi, double* out_dev) {
@@ -319,17 +186,6 @@ int gaussian2d_f64(const double* in_dev, int X, int Y, double sigma, double trun
   return IA3_OK;
 }
 
-// scipy.stats.scoreatpercentile's index arithmetic: rank i, and whether the value is interpolated with rank i + 1
-void percentile_index(double per, long long nvox, long long* i, double* idx) {
-  *idx = per / 100. * (double)(nvox - 1);
-  *i = (long long)*idx;
-}
-double percentile_value(double idx, long long i, double s0, double s1) {
-  if ((double)i == idx) return s0;
-  const double w0 = (double)(i + 1) - idx, w1 = idx - (double)i;
-  return (s0 * w0 + s1 * w1) / (w0 + w1);
-}
-
 }  // namespace
 
 extern "C" {
@@ -354,7 +210,7 @@ int ia3_stack_percentiles_dev(const ia3_stack* s, const double* pers, int n, dou
     if (!(pers[i] >= 0 && pers[i] <= 100)) return set_error(IA3_EINVAL, "percentile must be in the range [0, 100]");
     percentile_index(pers[i], nvox, &lo[i], &idx[i]);
     ranks[2 * i] = lo[i];
-    ranks[2 * i + 1] = lo[i] + 1 < nvox ? lo[i] + 1 : lo[i];
+    ranks[2 * i + 1] = percentile_next(lo[i], nvox);
   }
   union { uint16_t u[MAXR]; float f[MAXR]; } v;
   rc = order_stats_host(s, ranks, 2 * n, &v); if (rc) return rc;

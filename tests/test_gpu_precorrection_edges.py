@@ -13,7 +13,7 @@ tests/test_precorrection_edges_cpu.py and tests/golden/precorr_edges.json).
   hot pixels     hot_vote_k / hot_vote_u16f_k on partial tiles, hot_compact_k's device list up to its last entry and
                  the host fallback one candidate later, hot_fix_k / hot_fix_u16f_k over thousands of candidates whose
                  order matters
-  z shift        second blocks of select_pick_k / select_finish_k, negative float32 keys, a median of 0, ties
+  z shift        second blocks of sel_pick_k / sel_median_k, negative float32 keys, a median of 0, ties
 
 The pointer-alignment fallbacks of launch_illum / launch_bleed are not reached: every allocation is aligned.
 """

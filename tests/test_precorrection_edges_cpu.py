@@ -207,7 +207,7 @@ def test_rescaled_mix_inputs():
 def test_z_shift_inputs():
     for name in ("z65", "z130"):
         Z = P.inputs("zshift/" + name)[0].shape[0]
-        assert 2 * (Z + 1) > 64 and Z + 1 > 64                       # second blocks of select_pick_k / select_finish_k
+        assert 2 * (Z + 1) > 64 and Z + 1 > 64                       # second blocks of sel_pick_k / sel_median_k
     f = P.inputs("zshift/f32neg")[0]
     assert f.dtype == np.float32 and (f < 0).sum() > 50 and (np.median(f, axis=(1, 2)) < 0).any()
     with np.errstate(all="ignore"):
