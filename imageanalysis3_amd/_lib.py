@@ -26,6 +26,7 @@ IA3_MORPH_ERODE, IA3_MORPH_DILATE, IA3_MORPH_CLOSE = 0, 1, 2   # ia3_binary_morp
 IA3_SELECT_THREADS, IA3_SELECT_TILE = 256, 256      # spots of a workgroup, candidates of an LDS tile
 IA3_SELECT_EMPTY = 1                                # ia3_select_chromosomes_dev: every candidate was removed
 IA3_PICK_MAX_CHANNELS = 8
+IA3_DENSITY_MAX_CELL = 65536                        # loci of one cell of a DensityPopulation
 IA3_MOVIE_MAXCH = 8
 # the names this module gave some of them before
 MODE_REFLECT, MODE_NEAREST, MODE_CONSTANT = IA3_MODE_REFLECT, IA3_MODE_NEAREST, IA3_MODE_CONSTANT
@@ -279,6 +280,10 @@ PROTOTYPES = {
     "ia3_dist_free": (None, [_H]),
     "ia3_dist_summary_dev": (_I, [_H, _IP, _IP, _I, _I, _I, _I, _I, _D, _DP, _IP, _IP]),
     "ia3_dist_contact_stack_dev": (_I, [_DP, _LL, _LL, _D, _DP, _IP, _IP]),
+    # A/B compartment densities of traced cells
+    "ia3_density_create": (_I, [_DP, _IP, _IP, _IP, _I, _I, _H]),
+    "ia3_density_free": (None, [_H]),
+    "ia3_density_scores_dev": (_I, [_H, _BP, _DP, _I, _I, _I, _DP, _IP]),
     # whole round-folder movies
     "ia3_process_movies": (_I, [_MOVJ, _I, _MOVP]),
 }
@@ -1385,3 +1390,127 @@ def dist_contact_stack(stack, contact_th, return_counts=False):
     nf, nc = np.empty(v.shape[1:], dtype=np.int32), np.empty(v.shape[1:], dtype=np.int32)
     check(lib().ia3_dist_contact_stack_dev(ptr(v), N, K, float(contact_th), ptr(prob), ptr(nf), ptr(nc)))
     return (prob, nf, nc) if return_counts else prob
+
+
+class DensityLayout(object):
+    """The loci of a list of cells (each a dict ``chr -> (H, R, 3)`` coordinates) packed for ``ia3_density_create``, host
+    arrays only.  Points run cell by cell, inside a cell chromosome by chromosome in the dict's order, then homolog, then
+    region.  ``copy_of`` numbers the (chromosome, homolog) of a point within its cell, ``locus_of`` is ``first_id[chr] +
+    region`` with the chromosomes laid out in the order of ``chrs`` and ``regions[chr]`` the largest R any cell has;
+    ``least_regions[chr]`` is the smallest, the bound an index of the labels must respect.  ``blocks[cell]`` lists
+    ``(chr, H, R, first point)``."""
+
+    def __init__(self, cells, chrs):
+        chrs = list(chrs)
+        known = set(chrs)
+        self.chrs = chrs
+        self.regions = {c: 0 for c in chrs}
+        self.least_regions = {}
+        tables, self.blocks = [], []
+        start = [0]
+        for i, cell in enumerate(cells):
+            blocks, at = [], start[-1]
+            for c, zxys in cell.items():
+                if c not in known:
+                    raise KeyError(c)
+                a = np.asarray(zxys, dtype=np.float64)
+                if a.ndim != 3 or a.shape[0] < 1 or a.shape[1] < 1 or a.shape[2] != 3:
+                    raise ValueError("cell %d, chromosome %r: (homologs >= 1, regions >= 1, 3) coordinates are required, got "
+                                     "shape %s" % (i, c, a.shape))
+                H, R = a.shape[:2]
+                self.regions[c] = max(self.regions[c], R)
+                self.least_regions[c] = min(self.least_regions.get(c, R), R)
+                blocks.append((c, H, R, at))
+                tables.append(a.reshape(-1, 3))
+                at += H * R
+            if at - start[-1] > IA3_DENSITY_MAX_CELL:
+                raise ValueError("cell %d has %d loci (at most %d are built)" % (i, at - start[-1], IA3_DENSITY_MAX_CELL))
+            self.blocks.append(blocks)
+            start.append(at)
+        self.first_id, n = {}, 0
+        for c in chrs:
+            self.first_id[c] = n
+            n += self.regions[c]
+        self.n_loci = n
+        self.cell_start = np.array(start, dtype=np.int32)
+        self.n_points = int(start[-1])
+        self.zxys = np.ascontiguousarray(np.concatenate(tables, axis=0)) if tables else np.zeros((0, 3))
+        self.copy_of = np.zeros(self.n_points, dtype=np.int32)
+        self.locus_of = np.zeros(self.n_points, dtype=np.int32)
+        self.n_copies = np.zeros(len(self.blocks), dtype=np.int32)
+        for i, blocks in enumerate(self.blocks):
+            copy = 0
+            for c, H, R, at in blocks:
+                self.copy_of[at:at + H * R] = copy + np.repeat(np.arange(H, dtype=np.int32), R)
+                self.locus_of[at:at + H * R] = self.first_id[c] + np.tile(np.arange(R, dtype=np.int32), H)
+                copy += H
+            self.n_copies[i] = copy
+
+    def multiplicities(self, chr_2_AB_dict):
+        """The (n_loci, 2) uint8 table of a scoring call: how often region r of a chromosome is listed under 'A' and 'B'.
+        KeyError for a chromosome of the cells that the dict lacks; IndexError for an index outside 0..R-1 (negative ones
+        too: the reference wraps them for trans and drops them for cis, which is not restated) or one that is no integer."""
+        mult = np.zeros((max(self.n_loci, 1), 2), dtype=np.uint8)
+        for c, R in self.least_regions.items():
+            labels = chr_2_AB_dict[c]
+            for k, key in enumerate(('A', 'B')):
+                idx = np.asarray(labels[key])
+                if idx.size == 0:
+                    continue
+                if idx.dtype.kind not in "iu":
+                    raise IndexError("chr_2_AB_dict[%r][%r]: arrays used as indices must be of integer type" % (c, key))
+                idx = idx.astype(np.int64).ravel()
+                if idx.min() < 0 or idx.max() >= R:
+                    raise IndexError("chr_2_AB_dict[%r][%r]: an index outside 0..%d" % (c, key, R - 1))
+                n = np.bincount(idx, minlength=self.regions[c])
+                if n.max() > 255:
+                    raise NotImplementedError("chr_2_AB_dict[%r][%r] lists a region %d times (at most 255 are built)" % (c, key, n.max()))
+                mult[self.first_id[c]:self.first_id[c] + self.regions[c], k] = n
+        return mult
+
+    def unpack(self, values):
+        """``values``: (2, n_points).  The reference's list of per-cell dicts ``chr -> {'A': (H, R), 'B': (H, R)}``."""
+        return [{c: {'A': values[0, at:at + H * R].reshape(H, R).copy(), 'B': values[1, at:at + H * R].reshape(H, R).copy()}
+                 for c, H, R, at in blocks} for blocks in self.blocks]
+
+
+class DensityPopulation(Owner):
+    """The loci of a list of cells resident in HBM (owner of an ``ia3_density_population`` handle); ``scores`` gives every
+    locus its A and B sums for one set of labels, sigmas and flags without moving a coordinate again."""
+
+    def __init__(self, handle, layout):
+        self._h = handle
+        self.layout = layout
+        self.n_points = layout.n_points
+
+    @classmethod
+    def upload(cls, cells, chr_2_AB_dict_layout):
+        """``cells``: dicts ``chr -> (H, R, 3)``; ``chr_2_AB_dict_layout``: the chromosomes that the label dicts of the
+        scoring calls will name, in the order of the locus table (a ``chr_2_AB_dict`` itself will do).  KeyError for a
+        chromosome of a cell that is not among them."""
+        layout = cells if isinstance(cells, DensityLayout) else DensityLayout(cells, chr_2_AB_dict_layout)
+        if len(layout.blocks) < 1:
+            raise ValueError("DensityPopulation.upload: no cells")
+        h = C.c_void_p()
+        zxys = layout.zxys if layout.n_points else np.zeros((1, 3))
+        copy_of = layout.copy_of if layout.n_points else np.zeros(1, dtype=np.int32)
+        locus_of = layout.locus_of if layout.n_points else np.zeros(1, dtype=np.int32)
+        check(lib().ia3_density_create(ptr(zxys), ptr(layout.cell_start), ptr(copy_of), ptr(locus_of), len(layout.blocks),
+                                       max(layout.n_loci, 1), C.byref(h)))
+        return cls(h, layout)
+
+    def scores(self, mult, s2, use_cis=False, use_trans=True, exclude_self=True):
+        """``ia3_density_scores_dev``: (sums (2, n_points) float64, counts (2, n_points) int32), row 0 for A and row 1 for
+        B, from the (n_loci, 2) uint8 multiplicities and the three squared sigmas."""
+        mult = np.ascontiguousarray(mult, dtype=np.uint8)
+        s2 = np.ascontiguousarray(s2, dtype=np.float64)
+        if mult.shape != (max(self.layout.n_loci, 1), 2) or s2.shape != (3,):
+            raise ValueError("DensityPopulation.scores: multiplicities of shape %s and sigmas of shape %s" % (mult.shape, s2.shape))
+        sums = np.zeros((2, self.n_points), dtype=np.float64)
+        counts = np.zeros((2, self.n_points), dtype=np.int32)
+        check(lib().ia3_density_scores_dev(self._h, ptr(mult), ptr(s2), 1 if use_cis else 0, 1 if use_trans else 0,
+                                           1 if exclude_self else 0, ptr(sums), ptr(counts)))
+        return sums, counts
+
+    def _release(self, handle):
+        lib().ia3_density_free(handle)

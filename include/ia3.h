@@ -823,6 +823,31 @@ int ia3_dist_summary_dev(ia3_dist_population* h, const int* pair_a, const int* p
 int ia3_dist_contact_stack_dev(const double* stack, long long N, long long K, double contact_th, double* prob, int* n_finite,
                                int* n_contact);
 
+/* ---- A/B compartment densities of traced cells (density.hip) --------------------------------------------------
+ * compartment_tools/density.py:4-102: for every locus of every cell, the sum over the A loci and over the B loci of the
+ * cell's other chromosome copies (trans) and / or of its own copy (cis) of
+ *   exp(t),  t = -0.5 * ((dz*dz / s2[0] + dx*dx / s2[1]) + dy*dy / s2[2]),  d = contributor - query,
+ * every operation of t rounded to float64 on its own (csrc/ia3_density.h) and exp the device library's float64 exp.
+ * A population is the packed n_points x 3 float64 (z, x, y) loci of n_cells cells, cell c = points cell_start[c] ..
+ * cell_start[c + 1] (at most IA3_DENSITY_MAX_CELL of them); copy_of[p] numbers the point's (chromosome, homolog) within its
+ * cell (0 .. IA3_DENSITY_MAX_CELL - 1) and locus_of[p] in 0 .. n_loci - 1 names its (chromosome, region).  It is uploaded
+ * once and stays resident; a point with a coordinate that is not finite contributes to no sum.
+ * A scoring call names, per locus id, how often it counts as A and as B: mult[2 * id] and mult[2 * id + 1].  A contributor
+ * of another copy weighs use_trans ? mult : 0, one of the query's own copy use_cis && mult > 0 ? 1 : 0, and with exclude_self
+ * the query itself 0.  sums[k * n_points + p] (k = 0: A, 1: B) is the weighted sum of point p, added as partial sums of at
+ * most 64 consecutive contributors and then the partial sums in order (no atomics: the same bits on every run, whatever
+ * other cells the population holds); NaN for a query with a NaN coordinate.  counts[k * n_points + p] is the sum of the
+ * weights, the number of rows the reference would add.  Host pointers; per call 2 n_loci + 24 bytes go up and
+ * 24 n_points come down.  IA3_EINVAL: a null pointer, n_cells < 1, n_loci < 1, a cell_start that does not begin at 0 or
+ * falls, a cell above the cap, an id out of range, neither use_cis nor use_trans.  The handle is an
+ * ia3_density_population of density.hip. */
+#define IA3_DENSITY_MAX_CELL 65536
+int ia3_density_create(const double* zxys, const int* cell_start, const int* copy_of, const int* locus_of, int n_cells,
+                       int n_loci, void** out);
+void ia3_density_free(void* h);
+int ia3_density_scores_dev(void* h, const unsigned char* mult, const double* s2, int use_cis, int use_trans, int exclude_self,
+                           double* sums, int* counts);
+
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
  * Per movie: raw (frames, X, Y) uint16 movie from host memory or a .dax file -> split_im_by_channels
