@@ -17,7 +17,7 @@ IA3_MODE_REFLECT, IA3_MODE_NEAREST, IA3_MODE_CONSTANT = 0, 1, 2
 (IA3_TUNE_GAUSS_CERT, IA3_TUNE_DFT_VALU, IA3_TUNE_UPLOAD_THREADS, IA3_TUNE_SEED_DENSE, IA3_TUNE_FIT_NBLIST, IA3_TUNE_FFT_C2C,
  IA3_TUNE_FIT_FUSE, IA3_TUNE_GAUSS_FOLD, IA3_TUNE_SEED_STRIPS, IA3_TUNE_FIT_WAVES, IA3_TUNE_FIT_MERGE, IA3_TUNE_WARP_ONEPASS,
  IA3_TUNE_FIT_KDQ, IA3_TUNE_FIT_MEMO, IA3_TUNE_SEED_FUSED, IA3_TUNE_SEED_SKIP, IA3_TUNE_COL_RTC, IA3_TUNE_SEED_BGORDER,
- IA3_TUNE_DIST_TILE) = range(1, 20)
+ IA3_TUNE_DIST_TILE, IA3_TUNE_FIT_PAIR) = range(1, 21)
 IA3_DEBUG_FIT_MAXFEV, IA3_DEBUG_FIT_WAITBOUND = 100, 101
 IA3_BLUR_MAX_GB = 32
 IA3_BLUR_DIVIDE, IA3_BLUR_SUBTRACT = 0, 1           # ia3_blurnorm2d modes

@@ -17,7 +17,8 @@
 // lane computes residual + float32-rounded Jacobian row for its slots (float64, as NumPy does for
 // the reference under numpy>=2) and accumulates its share of JᵀJ (55) and Jᵀr (10); permlane swaps
 // and DPP rotations sum across the wave.  The 10x10 trust-region algebra (ia3_lm.h) runs redundantly on
-// all lanes on a per-wave LDS work area, so control flow stays wave-uniform.
+// all lanes of a half-wave on an LDS work area per fit: one fit in both halves, or the two fits of a seed without
+// neighbours in a half each (wave_gaussfit), so control flow stays uniform in a half.
 //
 // Roofline: ~0.2 kflop per voxel per evaluation, 2 KB gathered per fit -> f64-VALU-bound, not HBM
 // or MFMA (a 10x10 normal matrix is far below an MFMA tile).
@@ -71,6 +72,7 @@ struct FitArgs {
   const double* seeds;      // n x 3
   int n;                    // number of seeds (all fields)
   int fuse;                 // a seed without neighbours: first fit and sweep 1 by the same wave (see fit_stages_k)
+  int pair;                 // ... and both in one call of the driver, the solver a half-wave each (wave_gaussfit)
   int nb_cap;               // lists longer than this are not used (BALL_NBLIST; lowered by IA3_TUNE_FIT_NBLIST in tests)
   double nb_r2;             // (2r)²: seeds closer than this interact
   const int* nbr_cnt;       // n: number of neighbours of seed i (NOT clamped: > BALL_NBLIST = list overflow, see each_neighbour)
@@ -324,12 +326,16 @@ __device__ __forceinline__ void natural_wave(const IA3_LDS double* sc, IA3_LDS f
 struct BallLds { float dat[SLOTS][64], cz[SLOTS][64], cx[SLOTS][64], cy[SLOTS][64]; };   // [slot][lane]: 8 KB per wave
 struct WaveLds {
   BallLds bl;            // float32 data the fit sees (GaussianFit casts to float32, :172) and voxel coordinates
-  LMWork w;
-  FitCfg cfg;
+  // Two solver contexts: slot 0 is the fit whose row the seed keeps; slot 1 is used by the two fits of a seed without
+  // neighbours (run_position mode 2), where it holds the first fit while slot 0 holds the refit (wave_gaussfit)
+  LMWork w[2];
+  LMState st[2];         // the solver's state between two evaluations (lm_advance)
+  FitCfg cfg[2];
   double gsc[64];        // geom_scalars_wave
   double lo10[10], hi10[10];   // the ten smallest / largest voxel values, each ascending (start point, :175-182)
-  float p[12];           // the fit's row
+  float p[2][12];        // the fits' rows
   float co[4];           // centre of the previous fit of the seed (convergence test)
+  int so, nfev;          // run_position: that fit's success flag; function evaluations of the position's fits so far
   // tallies of this wave, flushed with one atomic each when the wave leaves the kernel: the per-fit atomics on three
   // shared cache lines (counters, stage control, n_iter) were the kernel's largest wait at two waves per SIMD — 43 us
   // per work-list position behind the ticket draw, which queues behind them (profiles/r03a/fit_stamps.log)
@@ -374,20 +380,25 @@ struct WaveLds {
 #define IA3_STAMP_FIT_END(L, n) do { } while (0)
 #endif
 
-// Wave-parallel evaluation of |f|, JᵀJ, Jᵀf for lm_solve.
+// Wave-parallel evaluation of |f|, JᵀJ, Jᵀf for lm_advance: the evaluation that the state of fit f (wave-uniform: slot
+// 0 or 1 of WaveLds) asks for, at that fit's point, with that fit's cfg, into that fit's trial area.  Always the full
+// wave, one fit at a time: the 64 partial sums per value and their summation tree are the same whichever slot is served.
 struct WaveEval {
   IA3_LDS WaveLds* L;
   unsigned valid;     // bit s: slot s of this lane holds a voxel
-  __device__ __forceinline__ double eval(const double* x, double* A, double* g) {
+  __device__ __forceinline__ double eval(const int f) {
     IA3_STAMP(L, 9);   // algebra since the last evaluation (or the fit's set-up before the first)
+    const IA3_LDS LMWork& wf = L->w[f];
+    const IA3_LDS double* x = __builtin_amdgcn_readfirstlane(L->st[f].first) ? wf.x : wf.xt;
+    const IA3_LDS double* A = __builtin_amdgcn_readfirstlane(L->st[f].cur) ? wf.A : wf.A1;
     Geom gm;   // wave-uniform coefficient tables, in scalar registers: the slot loop below reads them as SGPR operands
     const IA3_LDS BallLds* bl = &L->bl;
     {
       Geom g0;
       {
         GeomScalars gs;
-        geom_scalars_wave((const IA3_LDS double*)x, L->cfg, gs, L->gsc);
-        const double xh[2] = {0.0, ((const IA3_LDS double*)x)[1]};
+        geom_scalars_wave(x, L->cfg[f], gs, L->gsc);
+        const double xh[2] = {0.0, x[1]};
         geom_assemble(xh, gs, g0);
       }
       gm.h = sgpr(g0.h); gm.ebk_f = sgpr(g0.ebk_f); gm.ebk_j = sgpr(g0.ebk_j);
@@ -463,7 +474,6 @@ struct WaveEval {
         const double tot = row_sum16(q2[16]);
         if ((lane & 15) == 0 && 64 + sel < NV) dst[64 + sel] = tot;
       }
-      (void)g;
       __builtin_amdgcn_wave_barrier();   // A, g live in LDS: later reads by every lane follow these writes in order
     }
     // MINPACK's enorm (scaled sums) returns NaN, not inf, as soon as two components are infinite (inf/inf) or one
@@ -534,20 +544,38 @@ __device__ __forceinline__ void wave_extremes(const double* vals, unsigned valid
   __builtin_amdgcn_wave_barrier();
 }
 
-// One GaussianFit(...).fit() on the ball parked in L->bl (n >= 10 checked by the caller); start point from L->lo10 /
-// L->hi10 (the float64 data before the float32 cast, :175-182).  The row goes to L->p.  centre_only: the caller needs
-// nothing but the fitted centre p[1..3] (the first of two fits of a seed without neighbours): natural parameters and
-// eps are left out.
-__device__ __forceinline__ int wave_gaussfit(const FitArgs& fa, IA3_LDS WaveLds* L, unsigned valid, int kind, const double* c0,
-                                             double delta, int n, bool centre_only) {
-  IA3_LDS FitCfg& cfg_sh = L->cfg;   // wave-uniform: every lane writes the same values
-  cfg_sh.min_ws = fa.min_ws; cfg_sh.max_ws = fa.max_ws; cfg_sh.delta = delta; cfg_sh.init_w = fa.init_w;
+// GaussianFit(...).fit() on the ball parked in L->bl (n >= 10 checked by the caller), for ONE fit (nfit = 1: slot 0 of
+// WaveLds) or for TWO fits on the same ball that share nothing but the voxels and L->lo10 / L->hi10 (nfit = 2: slot 0 with
+// kind0 / delta0, slot 1 with kind1 / delta1 — the refit and the first fit of a seed without neighbours).  Start point
+// from L->lo10 / L->hi10 (the float64 data before the float32 cast, :175-182); the rows go to L->p[slot].  Returns the
+// function evaluations of its fits and adds them to L->nfev.
+//
+// The evaluations are made one after the other by the full wave (WaveEval::eval), so the sums are the ones a lone fit
+// gets.  The solver between two evaluations (lm_advance: 1.6 Cholesky factorisations and the substitutions of lm_par, a
+// dependent chain that every lane of a lone fit's wave executes identically) runs for both fits at once, lanes 0-31 on
+// slot 0 and lanes 32-63 on slot 1: work areas and solver state are addressed per lane (base of my slot + constant
+// offset), the control flow of the two halves diverges under the exec mask, each fit stops when its own state says so
+// (at most maxfev evaluations each) and the loop ends when neither wants another evaluation.  With one fit both halves
+// work on slot 0 and the control flow stays wave-uniform.
+// centre_only_last: of the fit in slot nfit - 1 the caller needs nothing but the fitted centre p[1..3] (the first of the
+// two fits of a seed without neighbours), and gets it in L->co: natural parameters and eps are left out.
+__device__ __forceinline__ int wave_gaussfit(const FitArgs& fa, IA3_LDS WaveLds* L, unsigned valid, int nfit, int kind0,
+                                             int kind1, const double* c0, double delta0, double delta1, int n,
+                                             bool centre_only_last) {
+  const int ln = threadIdx.x & 63;
+  // (opaque to the optimiser: what depends on the half and the kernel's arguments alone — my fit's delta, its kind —
+  // would otherwise be computed once per kernel and sit in vector registers, or their spill slots, through every other phase)
+  int lq = threadIdx.x;
+  asm volatile("" : "+v"(lq));
+  const int my = nfit == 2 ? (lq >> 5) & 1 : 0;   // the slot this lane's half works on
+  IA3_LDS FitCfg& cfg_sh = L->cfg[my];      // uniform in a half: every lane of it writes the same values
+  cfg_sh.min_ws = fa.min_ws; cfg_sh.max_ws = fa.max_ws; cfg_sh.delta = my ? delta1 : delta0; cfg_sh.init_w = fa.init_w;
   cfg_sh.c0[0] = c0[0]; cfg_sh.c0[1] = c0[1]; cfg_sh.c0[2] = c0[2];
   cfg_sh.variant = fa.variant; cfg_sh.iw[0] = fa.iw[0]; cfg_sh.iw[1] = fa.iw[1]; cfg_sh.iw[2] = fa.iw[2];
   __builtin_amdgcn_wave_barrier();
   const FitCfg& cfg = *(const FitCfg*)&cfg_sh;
-  LMWork& w = *(LMWork*)&L->w;
-  float* p_out = (float*)L->p;
+  LMWork& w = *(LMWork*)&L->w[my];
+  LMState& st = *(LMState*)&L->st[my];
   WaveEval ev;
   ev.L = L;
   ev.valid = valid;
@@ -555,42 +583,63 @@ __device__ __forceinline__ int wave_gaussfit(const FitArgs& fa, IA3_LDS WaveLds*
     double lo10[10], hi10[10];
 #pragma unroll
     for (int k = 0; k < 10; ++k) { lo10[k] = L->lo10[k]; hi10[k] = L->hi10[k]; }
-    init_guess(lo10, hi10, kind, cfg, w.x);
+    init_guess(lo10, hi10, my ? kind1 : kind0, cfg, w.x);
+    lm_begin(st);
   }
   __builtin_amdgcn_wave_barrier();
   IA3_STAMP(L, 3);   // fit set-up, start point
-  LMResult r = lm_solve(ev, w, fa.ftol, fa.xtol, fa.gtol, fa.maxfev, fa.factor);
+  bool want = true;   // my fit wants another evaluation
+#pragma unroll 1
+  for (;;) {
+    double fn = 0.0;
+    // (ONE evaluation site, in a rolled loop over the slots: the kernel is instruction-cache bound)
+#pragma unroll 1
+    for (int f = 0; f < nfit; ++f) {
+      if (__ballot(want && my == f) != 0ull) {   // wave-uniform
+        const double r = ev.eval(f);
+        if (my == f) fn = r;
+      }
+    }
+    if (want) want = lm_advance<32>(st, w, fn, fa.ftol, fa.xtol, fa.gtol, fa.maxfev, fa.factor);   // the halves diverge here
+    __builtin_amdgcn_wave_barrier();
+    if (__ballot(want) == 0ull) break;
+  }
   IA3_STAMP(L, 4);   // solver tail after the last evaluation
   // natural parameters and eps: the transcendental part once more through the lanes (geom_scalars_wave), at w.x
-  Geom gm;
-  {
-    GeomScalars gs;
-    // (the values stay in L->gsc after the call: nothing writes there before the next evaluation)
-    geom_scalars_wave((const IA3_LDS double*)L->w.x, L->cfg, gs, L->gsc);
-    if (centre_only) {
-      if ((threadIdx.x & 63) == 0) { L->p[1] = (float)gs.c[0]; L->p[2] = (float)gs.c[1]; L->p[3] = (float)gs.c[2]; }
-      __builtin_amdgcn_wave_barrier();
-      IA3_STAMP(L, 10);   // natural parameters, eps
-      IA3_STAMP_FIT_END(L, r.nfev);
-      return r.nfev;
+#pragma unroll 1
+  for (int f = nfit - 1; f >= 0; --f) {
+    Geom gm;
+    {
+      GeomScalars gs;
+      // (the values stay in L->gsc after the call: nothing writes there before the next evaluation)
+      geom_scalars_wave(L->w[f].x, L->cfg[f], gs, L->gsc);
+      if (centre_only_last && f == nfit - 1) {
+        if (ln == 0) { L->co[0] = (float)gs.c[0]; L->co[1] = (float)gs.c[1]; L->co[2] = (float)gs.c[2]; }
+        __builtin_amdgcn_wave_barrier();
+        IA3_STAMP(L, 10);   // natural parameters, eps
+        IA3_STAMP_FIT_END(L, L->st[f].nfev);
+        continue;
+      }
+      natural_wave(L->gsc, L->p[f]);
+      const double xh[2] = {0.0, L->w[f].x[1]};
+      geom_assemble(xh, gs, gm);
     }
-    natural_wave(L->gsc, L->p);
-    const double xh[2] = {0.0, L->w.x[1]};
-    geom_assemble(xh, gs, gm);
-  }
-  double s = 0.0;
-  const int ln = threadIdx.x & 63;
+    double s = 0.0;
 #pragma unroll
-  for (int sl = 0; sl < SLOTS; ++sl)
-    if (valid & (1u << sl))
-      s += fabs((gm.ebk_f + model_f0(gm, (double)L->bl.cz[sl][ln], (double)L->bl.cx[sl][ln], (double)L->bl.cy[sl][ln])) -
-                (double)L->bl.dat[sl][ln]);
-  const double eps = wave_sum(s) / (double)n;
-  if (ln == 0) L->p[10] = (float)eps;
+    for (int sl = 0; sl < SLOTS; ++sl)
+      if (valid & (1u << sl))
+        s += fabs((gm.ebk_f + model_f0(gm, (double)L->bl.cz[sl][ln], (double)L->bl.cx[sl][ln], (double)L->bl.cy[sl][ln])) -
+                  (double)L->bl.dat[sl][ln]);
+    const double eps = wave_sum(s) / (double)n;
+    if (ln == 0) L->p[f][10] = (float)eps;
+    __builtin_amdgcn_wave_barrier();
+    IA3_STAMP(L, 10);
+    IA3_STAMP_FIT_END(L, L->st[f].nfev);
+  }
+  const int nfev = L->st[0].nfev + (nfit == 2 ? L->st[1].nfev : 0);   // function evaluations of the call
+  if (ln == 0) L->nfev += nfev;
   __builtin_amdgcn_wave_barrier();
-  IA3_STAMP(L, 10);
-  IA3_STAMP_FIT_END(L, r.nfev);
-  return r.nfev;
+  return nfev;
 }
 
 // per-field tallies of the wave -> global memory (one atomic each; called when the wave moves on to another field and
@@ -628,13 +677,13 @@ __device__ __forceinline__ void store_result(const FitArgs& fa, int i, IA3_LDS W
                 "store_result writes SeedState by dwords");
   unsigned v = 0u;
   bool act = false;
-  if (lane < 20) { v = ((const IA3_LDS unsigned*)L->w.x)[lane]; act = ok; }
+  if (lane < 20) { v = ((const IA3_LDS unsigned*)L->w[0].x)[lane]; act = ok; }
   else if (lane < 22) { v = lane == 20 ? (unsigned)__double2loint(delta) : (unsigned)__double2hiint(delta); act = ok; }
   else if (lane == 22) { v = ok ? 1u : 0u; act = true; }
   else if (lane == 23) { v = 1u; act = ok; }
   else if (lane == 24) { v = cv ? 1u : 0u; act = write_conv; }
   else if (lane == 25) { v = (unsigned)LDH(&fa.state[i].ver) + 1u; act = ok; }   // only this wave ever writes the record
-  else if (lane >= 32 && lane < 43) { v = ((const IA3_LDS unsigned*)L->p)[lane - 32]; act = ok; }
+  else if (lane >= 32 && lane < 43) { v = ((const IA3_LDS unsigned*)L->p[0])[lane - 32]; act = ok; }
   unsigned* dst = lane < 32 ? (unsigned*)&fa.state[i] + lane : (unsigned*)&fa.ps[(size_t)i * 11] + (lane - 32);
   if (act) st_sc1(dst, v);
   if (lane == 0) {
@@ -878,10 +927,16 @@ __device__ __forceinline__ int gather_repeat(const FitArgs& fa, int i, IA3_LDS B
 //   float32 / integer data vs on the float64 residual).  The wave gathers the ball once, fits twice and hands over once;
 //   the work-list position of the seed's sweep 1 finds done[i] >= 2 and leaves.  Same operations on the same operands
 //   as the two separate positions; returns "converged".
-// The fit itself has ONE call site (the kernel is instruction-cache bound enough as it is).
+//   The two fits are independent of each other (the first fit's centre is needed only for the convergence test after
+//   both), so with FitArgs::pair (IA3_TUNE_FIT_PAIR, the default) ONE call of wave_gaussfit makes both: slot 0 of WaveLds
+//   the refit, whose row and state the seed keeps, slot 1 the first fit, of which only the centre is wanted (L->co).
+//   Their evaluations alternate, full wave each; the solver between two evaluations runs for both at once, a half-wave
+//   each.  Without it the same driver is called twice, one fit each time, first fit first.
+// The fit itself has ONE call site (the kernel is instruction-cache bound enough as it is); modes 0 and 1 run the same
+// driver with one fit.
 __device__ __forceinline__ bool run_position(const FitArgs& fa, IA3_LDS WaveLds* L, int i, int mode) {
   tally_field(fa, L, fa.fov_of[i]);
-  const double c0[3] = {fa.seeds[3 * i], fa.seeds[3 * i + 1], fa.seeds[3 * i + 2]};
+  const double* c0 = fa.seeds + 3 * (size_t)i;   // (read where the fit is set up: three doubles less to carry through the gather)
   unsigned valid = 0;
   int n;
   {
@@ -891,32 +946,38 @@ __device__ __forceinline__ bool run_position(const FitArgs& fa, IA3_LDS WaveLds*
     if (n >= NP) wave_extremes(vals, valid, L);   // mode 2: the same ten smallest / largest values start both fits
     IA3_STAMP(L, 2);   // extremes
   }
-  int success_old = 0;
-  float co0 = 0.f, co1 = 0.f, co2 = 0.f;
-  if (mode == 1) {
-    success_old = LDH(&fa.state[i].success);
-    co0 = LDH(&fa.ps[(size_t)i * 11 + 1]); co1 = LDH(&fa.ps[(size_t)i * 11 + 2]); co2 = LDH(&fa.ps[(size_t)i * 11 + 3]);
-  }
+  // the centre of the seed's previous fit waits in L->co for the convergence test: mode 1 the row of the last sweep,
+  // mode 2 what this wave's first fit leaves there (wave_gaussfit, centre_only_last)
   const bool ok = n >= NP;  // :382-383 (mode 2: for both fits, same voxels)
-  int nfev = 0, nfev_first = 0;
-  const int npass = mode == 2 ? 2 : 1;
+  // (as are that fit's success flag and the evaluation count, of both fits in mode 2: nothing but the position itself is
+  // carried through the fit in registers)
+  {
+    const int lane = threadIdx.x & 63;
+    if (lane < 3) { if (mode == 1) L->co[lane] = LDH(&fa.ps[(size_t)i * 11 + 1 + lane]); }
+    else if (lane == 3) L->so = mode == 1 ? LDH(&fa.state[i].success) : (ok ? 1 : 0);
+    else if (lane == 4) L->nfev = 0;
+    __builtin_amdgcn_wave_barrier();
+  }
+  const bool pair = mode == 2 && fa.pair;   // both fits from one call of the driver
+  const int npass = mode == 2 && !pair ? 2 : 1;
+  const int kind_first = fa.dtype == IA3_F32 ? 0 : 1;
 #pragma unroll 1
   for (int pass = 0; pass < npass; ++pass) {
-    const bool refit = mode == 1 || pass == 1;
-    if (pass == 1) { success_old = ok ? 1 : 0; co0 = L->p[1]; co1 = L->p[2]; co2 = L->p[3]; nfev_first = nfev; }
+    const bool refit = mode == 1 || pass == 1 || pair;   // (slot 0 of a pair is the refit, slot 1 the first fit)
     // a refit sees the float64 residual (kind 2) and casts it to float32 (:172); the first fit the stack's own dtype
-    if (ok) nfev = wave_gaussfit(fa, L, valid, refit ? 2 : (fa.dtype == IA3_F32 ? 0 : 1), c0,
-                                 refit ? fa.delta_repeat : fa.delta_first, n, mode == 2 && pass == 0);
+    if (ok) wave_gaussfit(fa, L, valid, pair ? 2 : 1, refit ? 2 : kind_first, kind_first, c0,
+                          refit ? fa.delta_repeat : fa.delta_first, fa.delta_first, n, mode == 2 && (pair || pass == 0));
   }
+  const int nfev = L->nfev;
   if (mode == 2 && ok && (threadIdx.x & 63) == 0) L->tally[0] += 1ull;   // two fits; store_result counts one
   // convergence (:677-680): float32 centre differences, compared in float64
   bool cv = true;
-  if (mode != 0 && ok && success_old) {
-    const float d0 = co0 - L->p[1], d1 = co1 - L->p[2], d2 = co2 - L->p[3];
+  if (mode != 0 && ok && L->so) {
+    const float d0 = L->co[0] - L->p[0][1], d1 = L->co[1] - L->p[0][2], d2 = L->co[2] - L->p[0][3];
     const float dist = (d0 * d0 + d1 * d1) + d2 * d2;
     cv = (double)dist < fa.dist_th2;
   }
-  store_result(fa, i, L, mode == 0 ? fa.delta_first : fa.delta_repeat, ok, n, nfev + nfev_first, mode != 0, cv);
+  store_result(fa, i, L, mode == 0 ? fa.delta_first : fa.delta_repeat, ok, n, nfev, mode != 0, cv);
   IA3_STAMP(L, 11);   // store_result
   return cv;
 }
@@ -1237,15 +1298,15 @@ __global__ __launch_bounds__(64, 2) void fit_voxels_k(VoxArgs va, int n_fits, do
   const double min_w = va.cfg[4 * i + 1], max_w = va.cfg[4 * i + 2];
   fa.min_ws = min_w * min_w; fa.max_ws = max_w * max_w; fa.init_w = va.cfg[4 * i + 3];
   fa.ftol = ftol; fa.xtol = xtol; fa.gtol = gtol; fa.maxfev = maxfev; fa.factor = factor;
-  const double c0[3] = {va.center[3 * i], va.center[3 * i + 1], va.center[3 * i + 2]};
-  if (lane < 11) L->p[lane] = NAN;
+  const double* c0 = va.center + 3 * (size_t)i;
+  if (lane < 11) L->p[0][lane] = NAN;
   __builtin_amdgcn_wave_barrier();
   int nfev = 0;
-  if (ok) nfev = wave_gaussfit(fa, L, valid, va.kind[i], c0, va.cfg[4 * i], n, false);
+  if (ok) nfev = wave_gaussfit(fa, L, valid, 1, va.kind[i], 0, c0, va.cfg[4 * i], 0.0, n, false);
   if (lane == 0) {
 #pragma unroll
-    for (int k = 0; k < 11; ++k) va.ps[(size_t)i * 11 + k] = L->p[k];
-    for (int k = 0; k < NP; ++k) va.xs[(size_t)i * NP + k] = ok ? L->w.x[k] : NAN;
+    for (int k = 0; k < 11; ++k) va.ps[(size_t)i * 11 + k] = L->p[0][k];
+    for (int k = 0; k < NP; ++k) va.xs[(size_t)i * NP + k] = ok ? L->w[0].x[k] : NAN;
     va.info[2 * i] = ok ? 1 : 0;
     va.info[2 * i + 1] = nfev;
   }
@@ -1331,6 +1392,7 @@ struct ia3_fitter {
 namespace {
 
 int g_nb_cap = BALL_NBLIST;   // IA3_TUNE_FIT_NBLIST
+int g_fit_pair = 1;     // IA3_TUNE_FIT_PAIR: 1 = those two fits from one call of wave_gaussfit, the solver a half-wave each
 int g_fit_fuse = 1;     // IA3_TUNE_FIT_FUSE: 1 = a seed without neighbours gets its first fit and sweep 1 from one wave
 int g_fit_maxfev = 0;   // IA3_DEBUG_FIT_MAXFEV: profiling only (splits the kernel time into a fixed and a per-evaluation part)
 int g_fit_waves = 2;    // IA3_TUNE_FIT_WAVES: persistent waves per SIMD (the kernel's 256 registers allow two)
@@ -1343,7 +1405,7 @@ FitArgs make_args(const ia3_fitter* f) {
   a.ims = (const void* const*)f->d_ims; a.fov_of = (const int*)f->d_fov_of; a.fov_start = (const int*)f->d_fov_start;
   a.n_fov = (int)f->ims.size(); a.fov_counters = (unsigned long long*)f->d_fov_counters;
   a.dtype = f->im->dtype; a.Z = f->im->Z; a.X = f->im->X; a.Y = f->im->Y;
-  a.n = f->n; a.fuse = g_fit_fuse; a.nb_cap = g_nb_cap; a.nb_r2 = 4.0 * f->prm.radius_fit * (double)f->prm.radius_fit;
+  a.n = f->n; a.fuse = g_fit_fuse; a.pair = g_fit_pair; a.nb_cap = g_nb_cap; a.nb_r2 = 4.0 * f->prm.radius_fit * (double)f->prm.radius_fit;
   a.seeds = (const double*)f->d_seeds; a.nbr_cnt = (const int*)f->d_nbr_cnt; a.nbr_idx = (const int*)f->d_nbr_idx;
   a.ball = (const int*)f->d_ball; a.nball = f->nball; a.radius = f->prm.radius_fit;
   a.tie_lost = f->ties_resolved ? (const unsigned long long*)f->d_tie_lost : nullptr;
@@ -1566,6 +1628,7 @@ namespace ia3k {
 void set_fit_nblist(int cap) { g_nb_cap = cap < 0 ? 0 : (cap > BALL_NBLIST ? BALL_NBLIST : cap); }
 int get_fit_nblist() { return g_nb_cap; }   // fastfit.hip reads its neighbour lists under the same knob
 void set_fit_fuse(int on) { g_fit_fuse = on ? 1 : 0; }
+void set_fit_pair(int on) { g_fit_pair = on ? 1 : 0; }
 void set_fit_maxfev(int n) { g_fit_maxfev = n; }
 void set_fit_waves(int n) { g_fit_waves = n < 1 ? 1 : (n > IA3_FIT_LB ? IA3_FIT_LB : n); }
 void set_fit_merge(int on) { g_fit_merge = on != 0; }

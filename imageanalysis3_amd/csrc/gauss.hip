@@ -925,6 +925,7 @@ int ia3_set_tuning(int key, int value) {
   if (key == IA3_TUNE_FIT_NBLIST) { ia3k::set_fit_nblist(value); return 0; }
   if (key == IA3_TUNE_FFT_C2C) { ia3k::set_fft_c2c(value); return 0; }
   if (key == IA3_TUNE_FIT_FUSE) { ia3k::set_fit_fuse(value); return 0; }
+  if (key == IA3_TUNE_FIT_PAIR) { ia3k::set_fit_pair(value); return 0; }
   if (key == IA3_TUNE_FIT_WAVES) { ia3k::set_fit_waves(value); return 0; }
   if (key == IA3_TUNE_FIT_MERGE) { ia3k::set_fit_merge(value); return 0; }
   if (key == IA3_TUNE_WARP_ONEPASS) { ia3k::set_warp_onepass(value); return 0; }

@@ -45,12 +45,16 @@ IA3_HD constexpr int tri(int i, int j) {  // packed upper-triangle index, i <= j
 
 // Element-wise sections (ten independent square roots or divisions, each a 20-30 instruction sequence on the GPU) run
 // on lanes 0..9 of the wave, one element per lane, instead of ten times on every lane: operands and results go through
-// the LDS-resident work area, the surrounding control flow stays wave-uniform.  Same operations on the same operands,
+// the LDS-resident work area, the surrounding control flow stays uniform in the group of lanes that works on one fit
+// (the wave, or a half-wave: lm_lane).  Same operations on the same operands,
 // so results are bit-identical to the serial form the host build uses.
 #if defined(__HIP_DEVICE_COMPILE__)
 #define IA3_LM_PAR 1
 #define IA3_LM_SYNC() __builtin_amdgcn_wave_barrier()
-// lane index inside a group of LW lanes (64: one fit per wave; 32: the paired solver of fit.hip, one fit per half-wave)
+// lane index inside a group of LW lanes: the ten element-wise lanes are lanes 0..9 of each group.  64: one fit per wave.
+// 32: one fit per half-wave, which is how fit.hip runs lm_advance — with two fits (wave_gaussfit, the two fits of a
+// seed without neighbours) lanes 0-31 work on one LMWork and lanes 32-63 on the other; with one fit both halves work on
+// the same area and lanes 32..41 repeat what lanes 0..9 do (same values to the same addresses).
 template <int LW> __device__ __forceinline__ int lm_lane() {
   return (int)__builtin_amdgcn_mbcnt_hi(~0u, __builtin_amdgcn_mbcnt_lo(~0u, 0u)) & (LW - 1);
 }
@@ -243,27 +247,49 @@ IA3_HD void lm_par(const double* A, const double* g, const double* diag, double 
 // lmder's iteration with ONE evaluation site: the evaluation at the start point is the first pass of the same loop
 // that evaluates the trial points (it is "accepted" unconditionally).  After an accepted point the outer-loop
 // prologue of lmder runs (column norms, scaling, gradient test), then lmpar and the next trial point.
-template <class Eval>
-IA3_HD LMResult lm_solve(Eval& ev, LMWork& w, double ftol, double xtol, double gtol, int maxfev,
-                         double factor) {
+//
+// The solver can be stopped at its evaluation: everything between two evaluations is lm_advance, a function of the
+// solver's state (LMState) and its work area.  lm_solve is the loop  eval -> lm_advance;  the paired driver of fit.hip
+// keeps two states and two work areas, evaluates the two fits one after the other with the full wave and advances
+// both at once, one fit per half-wave (LW = 32): the two fits share nothing.
+struct LMState {
+  double fnorm, par, delta, xnorm, gnorm, pnorm, jp2;
+  int first;         // the next evaluation is the one at the start point w.x (every later one is at w.xt)
+  int nfev, iter, info;
+  int cur;           // which half of LMWork holds JᵀJ / Jᵀf of the accepted point: 0 = A / g, 1 = A1 / g1
+};
+IA3_HD void lm_begin(LMState& s) {
+  s.fnorm = 0.0; s.par = 0.0; s.delta = 0.0; s.xnorm = 0.0; s.gnorm = 0.0; s.pnorm = 0.0; s.jp2 = 0.0;
+  s.first = 1; s.nfev = 0; s.iter = 1; s.info = 0; s.cur = 0;
+}
+// where the next evaluation is wanted: the point, and the half of the work area that takes JᵀJ / Jᵀf of it
+// (JᵀJ / Jᵀf of the accepted point and of the trial point ping-pong between the two halves of the work area:
+// accepting a step flips `cur` instead of copying 65 values through LDS)
+IA3_HD double* lm_eval_x(const LMState& s, LMWork& w) { return s.first ? w.x : w.xt; }
+IA3_HD double* lm_eval_A(const LMState& s, LMWork& w) { return s.cur ? w.A : w.A1; }
+IA3_HD double* lm_eval_g(const LMState& s, LMWork& w) { return s.cur ? w.g : w.g1; }
+
+// From the result fnorm1 of the evaluation lm_eval_x / lm_eval_A asked for up to the next one.  Returns whether another
+// evaluation is wanted; if not, s.info says why and w.x is the solution.
+template <int LW = 64>
+IA3_HD bool lm_advance(LMState& s, LMWork& w, const double fnorm1, double ftol, double xtol, double gtol, int maxfev,
+                       double factor) {
+  double* Ac = s.cur ? w.A1 : w.A; double* gc = s.cur ? w.g1 : w.g;      // current accepted point
+  double* At = s.cur ? w.A : w.A1; double* gt = s.cur ? w.g : w.g1;      // trial point (just evaluated)
+  double fnorm = s.fnorm, par = s.par, delta = s.delta, xnorm = s.xnorm, gnorm = s.gnorm, pnorm = s.pnorm, jp2 = s.jp2;
   LMResult r;
-  r.info = 0; r.nfev = 0; r.iter = 1;
-  // JᵀJ / Jᵀf of the accepted point and of the trial point ping-pong between the two halves of the work area:
-  // accepting a step swaps the pointers instead of copying 65 values through LDS
-  double* Ac = w.A; double* gc = w.g;      // current accepted point
-  double* At = w.A1; double* gt = w.g1;    // trial point
-  double fnorm = 0.0, par = 0.0, delta = 0.0, xnorm = 0.0, gnorm = 0.0, pnorm = 0.0, jp2 = 0.0;
-  bool first = true;
-  IA3_NOUNROLL
-  for (;;) {
-    const double fnorm1 = ev.eval(first ? w.x : w.xt, At, gt);
+  r.info = s.info; r.nfev = s.nfev; r.iter = s.iter;
+  bool first = s.first != 0;
+  int cur = s.cur;
+  bool more = true;
+  do {   // (one pass: `break` leaves for the state's write-back, as it left lmder's loop)
     ++r.nfev;
     bool accepted;
     if (first) {
       first = false;
       accepted = true;
       fnorm = fnorm1;
-      { double* sw = Ac; Ac = At; At = sw; sw = gc; gc = gt; gt = sw; }
+      { double* sw = Ac; Ac = At; At = sw; sw = gc; gc = gt; gt = sw; cur ^= 1; }
     } else {
       double actred = -1.0;
       if (0.1 * fnorm1 < fnorm) { double q = fnorm1 / fnorm; actred = 1.0 - q * q; }
@@ -289,7 +315,7 @@ IA3_HD LMResult lm_solve(Eval& ev, LMWork& w, double ftol, double xtol, double g
         double t[NP];
         IA3_UNROLL
         for (int j = 0; j < NP; ++j) { w.x[j] = w.xt[j]; t[j] = w.diag[j] * w.xt[j]; }
-        { double* sw = Ac; Ac = At; At = sw; sw = gc; gc = gt; gt = sw; }
+        { double* sw = Ac; Ac = At; At = sw; sw = gc; gc = gt; gt = sw; cur ^= 1; }
         xnorm = lm_norm(t);
         fnorm = fnorm1;
         ++r.iter;
@@ -298,17 +324,17 @@ IA3_HD LMResult lm_solve(Eval& ev, LMWork& w, double ftol, double xtol, double g
       if (small) r.info = 1;
       if (delta <= xtol * xnorm) r.info = 2;
       if (small && r.info == 2) r.info = 3;
-      if (r.info != 0) break;
+      if (r.info != 0) { more = false; break; }
       if (r.nfev >= maxfev) r.info = 5;
       if (fabs(actred) <= IA3_EPSMCH && prered <= IA3_EPSMCH && 0.5 * ratio <= 1.0) r.info = 6;
       if (delta <= IA3_EPSMCH * xnorm) r.info = 7;
       if (gnorm <= IA3_EPSMCH) r.info = 8;
-      if (r.info != 0) break;
+      if (r.info != 0) { more = false; break; }
     }
     if (accepted) {  // lmder's outer loop: Ac, gc hold JᵀJ, Jᵀf at x
 #if IA3_LM_PAR
       {
-        const int ln = lm_lane<64>();
+        const int ln = lm_lane<LW>();
         if (ln < NP) w.cn[ln] = sqrt(Ac[tri(ln, ln)]);
         IA3_LM_SYNC();
       }
@@ -331,7 +357,7 @@ IA3_HD LMResult lm_solve(Eval& ev, LMWork& w, double ftol, double xtol, double g
       if (fnorm != 0.0) {
 #if IA3_LM_PAR
         {
-          const int ln = lm_lane<64>();
+          const int ln = lm_lane<LW>();
           if (ln < NP) { const double cnl = w.cn[ln]; if (cnl != 0.0) w.sc[ln] = fabs((gc[ln] / fnorm) / cnl); }
           IA3_LM_SYNC();
         }
@@ -351,10 +377,10 @@ IA3_HD LMResult lm_solve(Eval& ev, LMWork& w, double ftol, double xtol, double g
         IA3_LM_SYNC();
 #endif
       }
-      if (gnorm <= gtol) { r.info = 4; break; }
+      if (gnorm <= gtol) { r.info = 4; more = false; break; }
 #if IA3_LM_PAR
       {
-        const int ln = lm_lane<64>();
+        const int ln = lm_lane<LW>();
         if (ln < NP) { const double dl = w.diag[ln], cl = w.cn[ln]; w.diag[ln] = dl > cl ? dl : cl; }
         IA3_LM_SYNC();
       }
@@ -365,7 +391,7 @@ IA3_HD LMResult lm_solve(Eval& ev, LMWork& w, double ftol, double xtol, double g
     }
     {  // lmder's inner loop up to the evaluation of the trial point
       double pv[NP], t[NP];
-      lm_par(Ac, gc, w.diag, delta, par, pv, w.sc);
+      lm_par<LW>(Ac, gc, w.diag, delta, par, pv, w.sc);
       IA3_UNROLL
       for (int j = 0; j < NP; ++j) {
         pv[j] = -pv[j];
@@ -379,12 +405,12 @@ IA3_HD LMResult lm_solve(Eval& ev, LMWork& w, double ftol, double xtol, double g
       jp2 = 0.0;
 #if IA3_LM_PAR
       {
-        const int ln = lm_lane<64>();
+        const int ln = lm_lane<LW>();
         if (ln < NP) {   // row ln of A times p, columns in ascending order as in the serial form
-          double s = 0.0;
+          double s_ = 0.0;
           IA3_UNROLL
-          for (int j = 0; j < NP; ++j) s += (ln <= j ? Ac[tri(ln, j)] : Ac[tri(j, ln)]) * pv[j];
-          w.sc[ln] = s;
+          for (int j = 0; j < NP; ++j) s_ += (ln <= j ? Ac[tri(ln, j)] : Ac[tri(j, ln)]) * pv[j];
+          w.sc[ln] = s_;
         }
         IA3_LM_SYNC();
         IA3_UNROLL
@@ -394,16 +420,30 @@ IA3_HD LMResult lm_solve(Eval& ev, LMWork& w, double ftol, double xtol, double g
 #else
       IA3_UNROLL
       for (int i = 0; i < NP; ++i) {
-        double s = 0.0;
+        double s_ = 0.0;
         IA3_UNROLL
-        for (int j = 0; j < NP; ++j) s += (i <= j ? Ac[tri(i, j)] : Ac[tri(j, i)]) * pv[j];
-        jp2 += pv[i] * s;
+        for (int j = 0; j < NP; ++j) s_ += (i <= j ? Ac[tri(i, j)] : Ac[tri(j, i)]) * pv[j];
+        jp2 += pv[i] * s_;
       }
 #endif
       if (jp2 < 0.0) jp2 = 0.0;
     }
-  }
-  r.fnorm = fnorm;
+  } while (false);
+  s.fnorm = fnorm; s.par = par; s.delta = delta; s.xnorm = xnorm; s.gnorm = gnorm; s.pnorm = pnorm; s.jp2 = jp2;
+  s.first = first ? 1 : 0; s.nfev = r.nfev; s.iter = r.iter; s.info = r.info; s.cur = cur;
+  return more;
+}
+
+template <class Eval>
+IA3_HD LMResult lm_solve(Eval& ev, LMWork& w, double ftol, double xtol, double gtol, int maxfev,
+                         double factor) {
+  LMState s;
+  lm_begin(s);
+  double fnorm1;
+  do fnorm1 = ev.eval(lm_eval_x(s, w), lm_eval_A(s, w), lm_eval_g(s, w));
+  while (lm_advance<64>(s, w, fnorm1, ftol, xtol, gtol, maxfev, factor));
+  LMResult r;
+  r.info = s.info; r.nfev = s.nfev; r.iter = s.iter; r.fnorm = s.fnorm;
   return r;
 }
 

@@ -164,6 +164,11 @@ int ia3_profile_collect(char* buf, int len); /* "kernel,count,total_ms\n" lines 
  * (64 lanes per entry) while 4 x 4 tiles would be fewer than two per compute unit, 4 x 4 (sixteen lanes per entry)
  * otherwise; 2, 4 or 8 = that tile for every shape (8 x 8: four lanes per entry).  Results are identical bit for bit. */
 #define IA3_TUNE_DIST_TILE 19
+/* IA3_TUNE_FIT_PAIR: 1 (default) = the two fits of a seed that IA3_TUNE_FIT_FUSE hands to one wavefront run together:
+ * the evaluations stay full-wave and one after the other, the trust-region algebra between two evaluations runs for
+ * both fits at once, one fit per half-wave; 0 = the same driver is called twice, one fit each time.  Tables are
+ * identical bit for bit. */
+#define IA3_TUNE_FIT_PAIR 20
 /* IA3_DEBUG_FIT_MAXFEV: PROFILING ONLY, changes results: > 0 caps the function evaluations of every fit (MINPACK's maxfev),
  * which splits the fit kernel's time into its fixed and its per-evaluation part; 0 (default) = the reference's limits. */
 #define IA3_DEBUG_FIT_MAXFEV 100

@@ -1,5 +1,5 @@
 """Per-phase shader cycles of the fit kernel (profiling build, scripts/fit_stamps.sh).
-usage: fit_stamps.py [Z X Y n layout dtype]"""
+usage: fit_stamps.py [Z X Y n layout dtype pair]      pair: IA3_TUNE_FIT_PAIR, 0 or 1 (default: the library's)"""
 import ctypes as C, sys, os
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -12,6 +12,9 @@ shape = tuple(int(v) for v in sys.argv[1:4]) if len(sys.argv) > 3 else (50, 2048
 n = int(sys.argv[4]) if len(sys.argv) > 4 else 5000
 layout = sys.argv[5] if len(sys.argv) > 5 else "isolated"
 dtype = sys.argv[6] if len(sys.argv) > 6 else "float32"
+if len(sys.argv) > 7:
+    L.check(lib.ia3_set_tuning(L.IA3_TUNE_FIT_PAIR, int(sys.argv[7])))
+    print("IA3_TUNE_FIT_PAIR", int(sys.argv[7]))
 im, c, h = synth.make_fov(shape, n, 3, layout=layout)
 if dtype == "uint16":
     im = np.clip(np.rint(im), 0, 65535).astype(np.uint16)
