@@ -1468,6 +1468,27 @@ static int ball_table(int radius, const int** d_ball, int* nball) {
   return IA3_OK;
 }
 
+// The width map w^2 = (max_w^2 - min_w^2) / (1 + exp(w_)) + min_w^2 has a start point only for min_w < init_w < max_w:
+// outside, the reference takes the logarithm of a non-positive number and returns NaN heights with success = True (or
+// divides by zero).  Refused before anything is launched.
+static int check_widths(double min_w, double max_w, double init_w, const char* what) {
+  if (!(min_w > 0.0) || !(min_w < max_w) || !(max_w < 1e150))
+    return set_error(IA3_EINVAL, "fit widths: 0 < min_w < max_w is required (min_w %g, max_w %g)", min_w, max_w);
+  if (!(init_w > min_w) || !(init_w < max_w))
+    return set_error(IA3_EINVAL, "fit widths: %s %g is not inside (min_w, max_w) = (%g, %g)", what, init_w, min_w, max_w);
+  return IA3_OK;
+}
+
+static int check_fit_widths(const ia3_fit_params* p) {
+  if (p->model_variant != 1) return check_widths(p->min_w, p->max_w, p->init_w, "init_w");
+  for (int k = 0; k < 3; ++k) {   // the start width make_args takes (Fitting_v3.py:71-79)
+    double w = p->init_w_zxy[k];
+    if (w * w > p->max_w || w * w < p->min_w) w = 1.5 * 1.5;
+    const int rc = check_widths(p->min_w, p->max_w, w, "init_w_zxy (as the legacy model takes it)"); if (rc) return rc;
+  }
+  return IA3_OK;
+}
+
 constexpr int MAX_FOV = 64;   // fields of view per fitter (their sweep counters share one 256-byte slot)
 struct FovSeeds { const ia3_stack* im; const double* host_zxy; const double* dev_zxy; int n; };
 
@@ -1477,6 +1498,7 @@ static int fit_create_impl(const FovSeeds* fovs, int n_fov, const ia3_fit_params
   dbg_stamp("fit_create enter");
   if (!fovs || n_fov < 1 || n_fov > MAX_FOV || !p || !out) return set_error(IA3_EINVAL, "bad argument");
   if (p->radius_fit < 1) return set_error(IA3_EINVAL, "radius_fit must be >= 1");
+  rc = check_fit_widths(p); if (rc) return rc;
   long long ntot = 0;
   for (int k = 0; k < n_fov; ++k) {
     const FovSeeds& q = fovs[k];
@@ -1906,7 +1928,9 @@ static int check_ctl(const StageCtl& hc) {
 // between pairs fetches the row table along with the control words: when nothing is left to refit (the common case)
 // ia3_fit_results finds everything on the host already and the fit costs ONE synchronisation.
 static int run_sweeps(ia3_fitter* f, int stage, bool fresh, int last = -1) {
-  if (last < 0) last = f->prm.n_max_iter + 2;   // sweeps 1 .. n_max_iter+1 (Fitting_v4.py:683)
+  // sweeps 1 .. n_max_iter+1 (Fitting_v4.py:683); the reference tests its limit after a sweep, so a negative one still
+  // gives the one sweep of n_max_iter = 0
+  if (last < 0) last = (f->prm.n_max_iter > 0 ? f->prm.n_max_iter : 0) + 2;
   f->cached = false;
   bool few_left = false;   // after the first pair: a handful of seeds still move (plateau twins that refit noise, a few chains)
   while (stage < last) {
@@ -2083,6 +2107,9 @@ int ia3_gaussfit_voxels(const double* vals, const int* coords_zxy, const int* of
     return set_error(IA3_EINVAL, "bad argument");
   if (n_fits == 0) return IA3_OK;
   const int total = off[n_fits];
+  for (int i = 0; i < n_fits; ++i) {
+    rc = check_widths(cfg4[4 * i + 1], cfg4[4 * i + 2], cfg4[4 * i + 3], "init_w"); if (rc) return rc;
+  }
   for (int i = 0; i < n_fits; ++i)
     if (off[i + 1] - off[i] > MAXBALL || off[i + 1] < off[i])
       return set_error(IA3_EUNSUPPORTED, "fit %d has %d voxels (> %d)", i, off[i + 1] - off[i], MAXBALL);

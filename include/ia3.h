@@ -391,9 +391,9 @@ typedef struct ia3_fit_params {
   int radius_fit;            /* 5 */
   double min_delta_center;   /* 1.0  (firstfit) */
   double max_delta_center;   /* 2.5  (repeatfit) */
-  int n_max_iter;            /* 10 */
+  int n_max_iter;            /* 10; the sweeps run are max(n_max_iter, 0) + 1 at most, as in the reference */
   double max_dist_th;        /* 0.1 */
-  double min_w, max_w, init_w; /* 0.5, 4, 1.5 */
+  double min_w, max_w, init_w; /* 0.5, 4, 1.5; 0 < min_w < init_w < max_w, anything else is IA3_EINVAL */
   /* 0: External/Fitting_v4.py (production).  1: External/Fitting_v3.py:50-262,312-425, the fitter behind the
    * legacy classes/__init__.py:57-88 `_fit_single_image`: per-axis start widths init_w_zxy (the reference's
    * global _sigma_zxy = 1.35, 1.9, 1.9), its to_center (:81-87) and MINPACK's default maxfev. */

@@ -17,13 +17,15 @@ SPOTS = np.array([[6.3, 10.2, 9.6], [7.1, 30.4, 11.2], [6.6, 50.7, 10.1], [12.4,
                   [17.2, 12.9, 52.3], [16.8, 33.5, 50.6], [17.5, 52.2, 51.4], [11.7, 44.1, 30.9]])
 
 
-def make_stack(spots, seed=7, noise=12.0, bg=400.0):
+def make_stack(spots, seed=7, noise=12.0, bg=400.0, widths=None, shape=SHAPE, dh=300.0):
+    """``widths``: (sz, sx, sy) of every spot (tests/harness/fitopt_cases.py); None: the widths of this module's spots;
+    ``dh``: the step from one spot's height to the next's"""
     rng = np.random.RandomState(seed)
-    z, x, y = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in SHAPE], indexing="ij")
-    im = bg + noise * rng.standard_normal(SHAPE)
+    z, x, y = np.meshgrid(*[np.arange(n, dtype=np.float64) for n in shape], indexing="ij")
+    im = bg + noise * rng.standard_normal(shape)
     for k, (cz, cx, cy) in enumerate(spots):
-        h = 2500.0 + 300.0 * k
-        sz, sx, sy = 1.2 + 0.05 * k, 1.6, 1.7 - 0.04 * k
+        h = 2500.0 + dh * k
+        sz, sx, sy = (1.2 + 0.05 * k, 1.6, 1.7 - 0.04 * k) if widths is None else widths[k]
         im += h * np.exp(-0.5 * (((z - cz) / sz) ** 2 + ((x - cx) / sx) ** 2 + ((y - cy) / sy) ** 2))
     return np.clip(im, 1.0, 65000.0)
 

@@ -101,11 +101,11 @@ def test_voxel_sets_equal_oracle(name):
         assert diff >= 1
 
 
-@pytest.mark.parametrize("radius", [2, 3])
+@pytest.mark.parametrize("radius", [2, 3, 4])
 def test_voxel_sets_equal_oracle_partly_filled_slot(radius):
-    """test_voxel_sets_equal_oracle's geometry at the radii whose ball ends inside a slot (30 and 120 voxels: slot 0 and
-    slot 1 partly filled) on the clustered fixture, where seeds lie within 2r of each other at both radii (the oracle alone
-    cuts 1 and 10 cells): voxel sets, their values and the first fit's voxel counts, exactly.  No fitted row is compared."""
+    """test_voxel_sets_equal_oracle's geometry at the radii whose ball ends inside a slot (30, 120 and 254 voxels: slot 0,
+    slot 1 partly filled, slot 3 filled up to two lanes) on the clustered fixture, where seeds lie within 2r of each other
+    at every one of them (the oracle alone cuts 1 and 10 cells at radius 2 and 3): voxel sets, their values and the first fit's voxel counts, exactly.  No fitted row is compared."""
     name = "clu_f32"
     im, seeds, _, fo = VR.oracle_fit(name, radius)
     whole = [VR.ball_voxels(c, radius, im.shape).shape[1] for c in seeds]
@@ -289,6 +289,30 @@ def test_isolated_seeds_first_fit_records():
     assert gap <= REC_MODEL_BAR
     for r, c in zip(f.ims_rec, seeds):
         assert r.shape == (VR.ball_voxels(c, RADIUS, im.shape).shape[1],)
+
+
+def test_records_carry_the_delta_center_of_their_fit():
+    """x11[:, 10] of the first-fit records is the caller's min_delta_center, of the current records after repeatfit() the
+    caller's max_delta_center — off the defaults, the first larger than the second — and each reconstruction is the host
+    model at its own record and delta to test 3's bar."""
+    import np_oracle as O
+    im = build_case("clu_f32")
+    seeds = O.get_seeds(im, th_seed=600)
+    f = _fitter(im, seeds, min_delta_center=1.75, max_delta_center=0.5)
+    f.firstfit()
+    gap0, x11_0, has0 = _model_gap(f, 0, seeds, im.shape)
+    has0 = has0.astype(bool)
+    assert has0.any() and (x11_0[has0, 10] == 1.75).all()
+    f.repeatfit()
+    gap1, x11_1, has1 = _model_gap(f, 1, seeds, im.shape)
+    _, x11_k, has_k = _model_gap(f, 0, seeds, im.shape)
+    has1, has_k = has1.astype(bool), has_k.astype(bool)
+    print("clu_f32 deltas 1.75 / 0.5: ims_rec vs host model first %.3g final %.3g (bar %.3g)" % (gap0, gap1, REC_MODEL_BAR))
+    assert has1.any() and (x11_1[has1, 10] == 0.5).all()
+    assert x11_k.tobytes() == x11_0.tobytes() and np.array_equal(has_k, has0)     # the first fit's records are kept
+    assert max(gap0, gap1) <= REC_MODEL_BAR
+    ps = np.array(f.ps)
+    assert (np.abs(ps[has1, 1:4] - seeds[has1]).max(axis=1) <= 0.5 + 1e-6).all()
 
 
 # ---- 7 -----------------------------------------------------------------------------------------------------------------

@@ -15,15 +15,19 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 SO = os.path.join(HERE, "native", "liblmcpu.so")
 
 
-@pytest.fixture(scope="module")
-def lm():
+def load_lm():
     src = os.path.join(HERE, "native", "lm_cpu.cpp")
     if not os.path.isfile(SO) or os.path.getmtime(SO) < os.path.getmtime(src):
         subprocess.check_call(["g++", "-O2", "-ffp-contract=off", "-shared", "-fPIC", "-o", SO, src])
     return C.CDLL(SO)
 
 
-def cfit(lm, vals, X, center, delta, kind):
+@pytest.fixture(scope="module")
+def lm():
+    return load_lm()
+
+
+def cfit(lm, vals, X, center, delta, kind, min_w=0.5, max_w=4.0, init_w=1.5):
     vals = np.ascontiguousarray(vals, dtype=np.float64)
     coords = np.ascontiguousarray(np.array(X).T, dtype=np.int32)
     p = np.zeros(11, np.float32)
@@ -31,9 +35,25 @@ def cfit(lm, vals, X, center, delta, kind):
     info = np.zeros(3, np.int32)
     c = np.array(center, dtype=np.float64)
     rc = lm.ia3cpu_gaussfit(vals.ctypes.data_as(C.c_void_p), coords.ctypes.data_as(C.c_void_p), C.c_int(len(vals)),
-                            c.ctypes.data_as(C.c_void_p), C.c_double(delta), C.c_double(0.5), C.c_double(4.0),
-                            C.c_double(1.5), C.c_int(kind), p.ctypes.data_as(C.c_void_p),
+                            c.ctypes.data_as(C.c_void_p), C.c_double(delta), C.c_double(min_w), C.c_double(max_w),
+                            C.c_double(init_w), C.c_int(kind), p.ctypes.data_as(C.c_void_p),
                             x.ctypes.data_as(C.c_void_p), info.ctypes.data_as(C.c_void_p))
+    return rc, p, x, info
+
+
+def cfit_v3(lm, vals, X, center, delta, kind, init_w=(1.35, 1.9, 1.9)):
+    """the legacy model (variant 1); its width bounds 0.5 / 4 are the class's"""
+    vals = np.ascontiguousarray(vals, dtype=np.float64)
+    coords = np.ascontiguousarray(np.array(X).T, dtype=np.int32)
+    iw = np.array([np.log((16.0 - w * w) / (w * w - 0.25)) for w in init_w])
+    p = np.zeros(11, np.float32)
+    x = np.zeros(10)
+    info = np.zeros(3, np.int32)
+    c = np.array(center, dtype=np.float64)
+    rc = lm.ia3cpu_gaussfit_v3(vals.ctypes.data_as(C.c_void_p), coords.ctypes.data_as(C.c_void_p), C.c_int(len(vals)),
+                               c.ctypes.data_as(C.c_void_p), C.c_double(delta), iw.ctypes.data_as(C.c_void_p),
+                               C.c_int(kind), p.ctypes.data_as(C.c_void_p), x.ctypes.data_as(C.c_void_p),
+                               info.ctypes.data_as(C.c_void_p))
     return rc, p, x, info
 
 
