@@ -28,6 +28,8 @@ IA3_SELECT_EMPTY = 1                                # ia3_select_chromosomes_dev
 IA3_PICK_MAX_CHANNELS = 8
 IA3_DENSITY_MAX_CELL = 65536                        # loci of one cell of a DensityPopulation
 IA3_MOVIE_MAXCH = 8
+IA3_CLOUD_F64, IA3_CLOUD_F32 = 0, 1                 # ia3_cloud_render modes
+IA3_CLOUD_MAX_S, IA3_CLOUD_MAX_KER_S, IA3_CLOUD_MAX_IMAGES, IA3_CLOUD_MAX_DIM = 4096, 511, 65535, 4096
 # the names this module gave some of them before
 MODE_REFLECT, MODE_NEAREST, MODE_CONSTANT = IA3_MODE_REFLECT, IA3_MODE_NEAREST, IA3_MODE_CONSTANT
 BLUR_DIVIDE, BLUR_SUBTRACT, BLUR_MAX_GB = IA3_BLUR_DIVIDE, IA3_BLUR_SUBTRACT, IA3_BLUR_MAX_GB
@@ -284,6 +286,10 @@ PROTOTYPES = {
     "ia3_density_create": (_I, [_DP, _IP, _IP, _IP, _I, _I, _H]),
     "ia3_density_free": (None, [_H]),
     "ia3_density_scores_dev": (_I, [_H, _BP, _DP, _I, _I, _I, _DP, _IP]),
+    # density clouds of traced chromosomes
+    "ia3_cloud_render_dev": (_I, [_DP, _IP, _I, _I, _I, _I, _I, _I, _H]),
+    "ia3_cloud_render": (_I, [_DP, _IP, _I, _I, _I, _I, _I, _H, _H]),
+    "ia3_cloud_gauss_ker": (_I, [_DP, _I, _DP, _DP]),
     # whole round-folder movies
     "ia3_process_movies": (_I, [_MOVJ, _I, _MOVP]),
 }
@@ -1514,3 +1520,102 @@ class DensityPopulation(Owner):
 
     def _release(self, handle):
         lib().ia3_density_free(handle)
+
+
+def cloud_sources(pos, h, sig, size_fold):
+    """The (n, 8) float64 source table of ``ia3_cloud_render``: pos[3], h, sig[3], size_fold per row; ``h``, ``sig`` (three
+    values) and ``size_fold`` are one value for all rows or one per row.  ValueError, before any device call, for a
+    position, sigma or size_fold that is not finite and for a box ``int(max(sig) * size_fold) + 1`` outside 1 ..
+    IA3_CLOUD_MAX_S + 1 (the library refuses the same)."""
+    pos = np.asarray(pos, dtype=np.float64)
+    if pos.ndim != 2 or pos.shape[1] != 3:
+        raise ValueError("cloud sources: positions of shape (n, 3) are required, got %s" % (pos.shape,))
+    n = len(pos)
+    t = np.empty((n, 8), dtype=np.float64)
+    t[:, :3] = pos
+    try:
+        t[:, 3] = np.asarray(h, dtype=np.float64)
+        t[:, 4:7] = np.asarray(sig, dtype=np.float64)
+        t[:, 7] = np.asarray(size_fold, dtype=np.float64)
+    except ValueError:
+        raise ValueError("cloud sources: h of shape () or (n,), sig of shape (3,) or (n, 3) and size_fold of shape () or (n,) "
+                         "are required for %d positions" % n)
+    if not np.isfinite(t[:, [0, 1, 2, 4, 5, 6, 7]]).all():
+        raise ValueError("cloud sources: a position, sigma or size_fold that is not finite")
+    with np.errstate(over="ignore"):
+        s = t[:, 4:7].max(axis=1) * t[:, 7] if n else np.zeros(0)
+    if not ((s > -1.0) & (s < IA3_CLOUD_MAX_S + 1.0)).all():
+        raise ValueError("cloud sources: a box of int(max(sig) * size_fold) + 1 outside 1 to %d" % (IA3_CLOUD_MAX_S + 1))
+    return t
+
+
+def _cloud_call(sources, image_start, shape, rounding):
+    sources = np.ascontiguousarray(sources, dtype=np.float64)
+    start = np.ascontiguousarray(image_start, dtype=np.int32)
+    shape = tuple(int(v) for v in shape)
+    if sources.ndim != 2 or sources.shape[1] != 8 or start.ndim != 1 or len(start) < 2 or start[0] != 0 \
+            or start[-1] != len(sources) or (np.diff(start) < 0).any():
+        raise ValueError("cloud render: an (n, 8) source table and offsets 0 .. n of its images are required")
+    if len(shape) != 3 or min(shape) < 1 or max(shape) > IA3_CLOUD_MAX_DIM or len(start) - 1 > IA3_CLOUD_MAX_IMAGES:
+        raise ValueError("cloud render: %d images of shape %s" % (len(start) - 1, shape))
+    dt = np.dtype(np.float64 if rounding is None else rounding)
+    if dt not in (np.dtype(np.float64), np.dtype(np.float32)):
+        raise ValueError("cloud render: rounding is None (float64) or numpy.float32, got %s" % (rounding,))
+    if len(sources) == 0:
+        sources = np.zeros((1, 8))     # a pointer for the call; no row of it is named
+    return sources, start, shape, dt, (IA3_CLOUD_F32 if dt == np.float32 else IA3_CLOUD_F64)
+
+
+def cloud_render(sources, image_start, shape, rounding=None, init=None):
+    """``ia3_cloud_render``: the (n_images,) + shape images of the source table ``sources`` (``cloud_sources``), image i from
+    the rows image_start[i] .. image_start[i + 1] in that order, started from ``init`` (same shape) or from zeros.
+    ``rounding`` None: float64 sums; ``numpy.float32``: float32 images rounded after every source."""
+    sources, start, shape, dt, mode = _cloud_call(sources, image_start, shape, rounding)
+    out = np.empty((len(start) - 1,) + shape, dtype=dt)
+    if init is not None:
+        init = np.ascontiguousarray(init, dtype=dt)
+        if init.shape != out.shape:
+            raise ValueError("cloud render: init of shape %s for images of shape %s" % (init.shape, out.shape))
+    check(lib().ia3_cloud_render(ptr(sources), ptr(start), len(start) - 1, shape[0], shape[1], shape[2], mode,
+                                 None if init is None else C.c_void_p(init.ctypes.data), C.c_void_p(out.ctypes.data)))
+    return out
+
+
+class CloudImages(Owner):
+    """Device memory for the images of ``ia3_cloud_render_dev`` (an ``ia3_buffer_alloc`` allocation of ``capacity`` bytes),
+    kept by a caller that renders many cells one after the other."""
+    _handle = "devptr"
+
+    def __init__(self, capacity):
+        self.capacity = int(capacity)
+        p = C.c_void_p()
+        check(lib().ia3_buffer_alloc(max(self.capacity, 8), C.byref(p)))
+        self.devptr = p
+
+    def render(self, sources, image_start, shape, rounding=None):
+        """Zero the first n_images images of ``shape``, render into them and download them."""
+        sources, start, shape, dt, mode = _cloud_call(sources, image_start, shape, rounding)
+        out = np.empty((len(start) - 1,) + shape, dtype=dt)
+        if out.nbytes > self.capacity:
+            raise ValueError("CloudImages.render: %d bytes of images in a buffer of %d" % (out.nbytes, self.capacity))
+        check(lib().ia3_cloud_render_dev(ptr(sources), ptr(start), len(start) - 1, shape[0], shape[1], shape[2], mode, 1,
+                                         self.devptr))
+        check(lib().ia3_buffer_download(self.devptr, out.nbytes, C.c_void_p(out.ctypes.data)))
+        return out
+
+    def _release(self, handle):
+        lib().ia3_buffer_free(handle)
+
+
+def cloud_gauss_ker(sig, s, disp):
+    """``ia3_cloud_gauss_ker``: the (s + 1,) * 3 float64 kernel of the reference's ``gauss_ker(sig, s, disp)``."""
+    sig = np.ascontiguousarray(sig, dtype=np.float64)
+    disp = np.ascontiguousarray(disp, dtype=np.float64)
+    s = int(s)
+    if sig.shape != (3,) or disp.shape != (3,):
+        raise ValueError("gauss_ker: three sigmas and three displacements are required, got %s and %s" % (sig.shape, disp.shape))
+    if s < 0 or s > IA3_CLOUD_MAX_KER_S:
+        raise ValueError("gauss_ker: sxyz %d (0 to %d)" % (s, IA3_CLOUD_MAX_KER_S))
+    out = np.empty((s + 1,) * 3, dtype=np.float64)
+    check(lib().ia3_cloud_gauss_ker(ptr(sig), s, ptr(disp), ptr(out)))
+    return out

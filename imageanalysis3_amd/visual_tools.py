@@ -1,7 +1,8 @@
-"""Drop-in for the two seeding functions of the reference's ``visual_tools.py`` that the legacy per-cell
-fitter (``classes/__init__.py:57-88 _fit_single_image``) calls: ``get_seed_points_base`` (:348-381) and
-``get_seed_in_distance`` (:1775-1870).  Filters, rank tests and compaction run on the device
-(``ia3_seed_in_distance``: seed.hip); the percentile threshold (``seed_by_per``) is evaluated here.
+"""Drop-in for the functions of the reference's ``visual_tools.py`` that run on the device here.
+
+The two seeding functions that the legacy per-cell fitter (``classes/__init__.py:57-88 _fit_single_image``) calls:
+``get_seed_points_base`` (:348-381) and ``get_seed_in_distance`` (:1775-1870).  Filters, rank tests and compaction run on
+the device (``ia3_seed_in_distance``: seed.hip); the percentile threshold (``seed_by_per``) is evaluated here.
 
 The reference functions use ``np.float`` / ``np.int`` (removed in NumPy 1.24); the semantics restated
 here are those of ``float`` / ``int`` which those aliases were.  Behaviours kept as written there:
@@ -9,6 +10,13 @@ here are those of ``float`` / ``int`` which those aliases were.  Behaviours kept
   ``background_gfilt_size`` (its default 10 applies) and, with a ``center``, the seeds stay in crop
   coordinates and are not distance-filtered (:1851-1858);
 * heights are int64 differences of the truncated rank-filter outputs; threshold test is a strict ``>``.
+
+The Gaussian sources: ``gauss_ker`` (:68-72), ``add_source`` (:87-110), ``subtract_source`` and ``plus_source`` (:112-116),
+and the flat batch form ``add_sources``, which is the loop of ``add_source`` over its rows as one launch
+(``ia3_cloud_render``: cloud.hip).  The box of a source and the argument of ``exp`` are NumPy's bit for
+bit, quirks included: kernel axis 0 pairs with ``sig[2]`` and the fractional part of ``pos[2]``, axis 1 with entry 0 and
+axis 2 with entry 1; the argument divides by ``sig**2`` before it squares; the last plane of every axis is never written.
+``exp`` is the device library's float64 one.  There is no CPU fallback.
 """
 import ctypes as C
 import numpy as np
@@ -110,3 +118,53 @@ def get_seed_in_distance(im, center=None, num_seeds=0, seed_radius=30,
         seeds = _call(im, None, num_seeds, seed_radius, gfilt_size, 10, filt_size, _th_seed,
                       False, 1, 0, hot_pix_th)
     return seeds.copy() if return_h else seeds[:, :3].copy()
+
+
+def gauss_ker(sig_xyz=[2, 2, 2], sxyz=16, xyz_disp=[0, 0, 0]):
+    """visual_tools.py:68-72 -- the (sxyz + 1,) * 3 float64 Gaussian box around ``sxyz / 2 + xyz_disp``, with the reference's
+    pairing of axes and entries (module docstring), computed on the device.  Only three dimensions are built."""
+    if len(xyz_disp) != 3 or len(sig_xyz) != 3:
+        raise NotImplementedError("gauss_ker: three dimensions run on the device, got %d displacements and %d sigmas"
+                                  % (len(xyz_disp), len(sig_xyz)))
+    if int(sxyz) != sxyz:
+        raise TypeError("gauss_ker: sxyz should be an integer, got %r" % (sxyz,))
+    return L.cloud_gauss_ker(sig_xyz, sxyz, xyz_disp)
+
+
+def add_sources(im_, pos, h, sig, size_fold=10, rounding=None):
+    """The loop ``for p, h_, s in rows: im = add_source(im, p, h_, s, size_fold)`` as one launch: ``pos`` (n, 3); ``h``,
+    ``sig`` (three values) and ``size_fold`` one value or one per row.  ``rounding=None``: the float64 result of that loop.
+    ``rounding=numpy.float32``: ``im_`` as float32 and the running image rounded to float32 after every source, which is
+    what assigning each result into a float32 array does (structure_tools/chromosome.py:35); a float32 result.
+    Rows that are not finite raise ``ValueError``; the input is never modified."""
+    im = np.asarray(im_)
+    if im.ndim != 3:
+        raise NotImplementedError("add_sources: three dimensions run on the device, got an image of shape %s" % (im.shape,))
+    if im.dtype.kind not in "uifb":
+        raise TypeError("add_sources: a real image is required, got %s" % im.dtype)
+    table = L.cloud_sources(pos, h, sig, size_fold)
+    return L.cloud_render(table, [0, len(table)], im.shape, rounding=rounding, init=im[None])[0]
+
+
+def add_source(im_, pos=[0, 0, 0], h=200, sig=[2, 2, 2], size_fold=10):
+    """visual_tools.py:87-110 -- a float64 copy of ``im_`` plus ``gauss_ker(sig, int(max(sig)*size_fold), frac(pos)) * h`` on
+    the clamped box around ``pos``: ``add_sources`` with one row."""
+    if len(pos) != 3 or len(sig) != 3:
+        raise NotImplementedError("add_source: three dimensions run on the device")
+    return add_sources(im_, np.asarray(pos, dtype=np.float64)[None], h, np.asarray(sig, dtype=np.float64), size_fold)
+
+
+def _fit_row_source(im, pfit, sign):
+    """A fit row (height, z, x, y, ..., three widths last) as one source of ``add_source``, its height times ``sign``."""
+    height, centre, widths = pfit[0], pfit[1:4], pfit[-3:]
+    return add_source(im, pos=centre, h=sign * height, sig=widths)
+
+
+def subtract_source(im, pfit):
+    """visual_tools.py:112-113 -- ``im`` minus the Gaussian of the fit row ``pfit``, at ``add_source``'s default ``size_fold``."""
+    return _fit_row_source(im, pfit, -1)
+
+
+def plus_source(im, pfit):
+    """visual_tools.py:115-116 -- ``im`` plus the Gaussian of the fit row ``pfit``."""
+    return _fit_row_source(im, pfit, 1)

@@ -853,6 +853,42 @@ void ia3_density_free(void* h);
 int ia3_density_scores_dev(void* h, const unsigned char* mult, const double* s2, int use_cis, int use_trans, int exclude_self,
                            double* sums, int* counts);
 
+/* ---- density clouds of traced chromosomes (cloud.hip) ---------------------------------------------------------
+ * visual_tools.py:68-72 gauss_ker, :87-116 add_source and the loop of structure_tools/chromosome.py:5-57
+ * convert_chr2Zxys_2_Cloud over the loci of a homolog.  A source is eight float64: pos[3], h, sig[3], size_fold.  With
+ *   s = int(max(sig) * size_fold),  pos_int = trunc(pos),  disp = -pos_int + pos,  pos_min = trunc(pos_int - (s + 1) / 2.)
+ * it adds, to every voxel i of [in_im(pos_min), in_im(pos_min + s + 1)) (in_im: >= shape becomes shape - 1, < 0 becomes 0,
+ * so the last plane of an axis is never written),
+ *   h * exp(t),  t = -((u0*u0 + u1*u1) + u2*u2) / 2.,  u_k = ((a_k - disp[k]) - s / 2.) / (sig[k]*sig[k]),
+ * where the kernel's coordinates (a_0, a_1, a_2) of voxel i are (i[1] - pos_min[1], i[2] - pos_min[2], i[0] - pos_min[0]):
+ * np.swapaxes(np.indices(...), 0, 3) pairs array axis 0 with disp[2] and sig[2], axis 1 with entry 0 and axis 2 with entry 1.
+ * Every operation of t is rounded to float64 on its own (csrc/ia3_cloud.h), t < -746 gives +0 and exp is the device
+ * library's float64 exp.  The n_images images of a call have one shape d0 x d1 x d2; image i takes the sources
+ * image_start[i] .. image_start[i + 1] of the table IN THAT ORDER.  mode IA3_CLOUD_F64: float64 images, acc = acc + h*exp(t)
+ * (add_source); IA3_CLOUD_F32: float32 images, acc = float32(float64(acc) + h*exp(t)) after every source (what assigning
+ * add_source's result into a float32 slice does, chromosome.py:35).  One launch for all images; a voxel's result does not
+ * depend on the other images of the call.  `sources` and `image_start` are host pointers in both forms.
+ *   ia3_cloud_render_dev   d_images is device memory (ia3_buffer_alloc) of n_images * d0 * d1 * d2 values of the mode's type,
+ *                          zeroed first when zero_first is set, else added to; it has been written when the call returns.
+ *   ia3_cloud_render       host images: `init` (the mode's type, or NULL for zeros) goes up and `out` comes down.
+ *   ia3_cloud_gauss_ker    the bare (s + 1)^3 float64 kernel of gauss_ker(sig, s, disp), host pointers; disp is any three
+ *                          values.  s is 0 .. IA3_CLOUD_MAX_KER_S.
+ * IA3_EINVAL, before any launch and before the device is touched: a null pointer, a mode other than the two, n_images outside
+ * 1 .. IA3_CLOUD_MAX_IMAGES, a dimension outside 1 .. IA3_CLOUD_MAX_DIM, an image_start that does not begin at 0 or falls,
+ * a source whose pos, sig or size_fold is NaN or infinite or whose s is outside 0 .. IA3_CLOUD_MAX_S.  A zero sigma is taken:
+ * IEEE division gives the reference's 0 or NaN.  A source whose box lies outside the image adds nothing. */
+#define IA3_CLOUD_F64 0
+#define IA3_CLOUD_F32 1
+#define IA3_CLOUD_MAX_S 4096
+#define IA3_CLOUD_MAX_KER_S 511
+#define IA3_CLOUD_MAX_IMAGES 65535
+#define IA3_CLOUD_MAX_DIM 4096
+int ia3_cloud_render_dev(const double* sources, const int* image_start, int n_images, int d0, int d1, int d2, int mode,
+                         int zero_first, void* d_images);
+int ia3_cloud_render(const double* sources, const int* image_start, int n_images, int d0, int d1, int d2, int mode,
+                     const void* init, void* out);
+int ia3_cloud_gauss_ker(const double* sig, int s, const double* disp, double* out);
+
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
  * Per movie: raw (frames, X, Y) uint16 movie from host memory or a .dax file -> split_im_by_channels
