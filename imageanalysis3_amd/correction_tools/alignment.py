@@ -18,6 +18,10 @@ from .. import _allowed_colors, _image_size, _num_buffer_frames, _num_empty_fram
 # default of scikit-image >= 0.19, checked against the oracle's restatement of the published algorithm only.
 DEFAULT_NORMALIZATION = None
 
+# ia3_align_image_dev and ia3_drift_ref_create take at most this many crops (csrc/movie.cpp, fft_align.hip: DriftRef); the
+# reference takes any number, so align_image measures a longer crop_list crop by crop.
+MAX_DEVICE_CROPS = 8
+
 
 def _find_boundary(_ct, _radius, _im_size):
     """correction_tools/alignment.py:80-85."""
@@ -76,6 +80,9 @@ class DriftReference(L.Owner):
     ``generate_drift_crops`` of the image size)."""
 
     def __init__(self, ref_im, crop_list=None, dtype=np.uint16):
+        if crop_list is not None and len(crop_list) > MAX_DEVICE_CROPS:
+            raise ValueError(f"a DriftReference keeps the spectra of at most {MAX_DEVICE_CROPS} crops, {len(crop_list)} "
+                             f"given: hand align_image the reference image itself for a longer crop_list")
         self._own = not isinstance(ref_im, L.DeviceStack)
         if self._own and not isinstance(ref_im, np.ndarray):
             raise IOError(f"Wrong input file type, {type(ref_im)} should be np.ndarray or a resident stack")
@@ -255,27 +262,50 @@ def align_image(
             _lims[:, :, 0] = np.maximum(_lims[:, :, 0], 0)
             _lims[:, :, 1] = np.minimum(_lims[:, :, 1], np.array(_src.shape)[None, :])
             _cl = np.ascontiguousarray(_lims, dtype=np.int32)
-            _out, _flag, _nused = (C.c_double * 3)(), C.c_int(0), C.c_int(0)
-            _each = np.zeros((len(_cl), 3), dtype=np.float64)
-            if _dref is not None:
-                L.check(L.lib().ia3_align_image_ref(_src._h, _dref._h, int(precision_fold),
-                                                    1 if DEFAULT_NORMALIZATION == "phase" else 0, int(min_good_drifts),
-                                                    float(drift_diff_th), _out, C.byref(_flag), L.dptr(_each),
-                                                    C.byref(_nused)))
-            else:
-                L.check(L.lib().ia3_align_image_dev(_src._h, _ref._h, L.ptr(_cl), len(_cl),
-                                                    int(precision_fold), 1 if DEFAULT_NORMALIZATION == "phase" else 0,
-                                                    int(min_good_drifts), float(drift_diff_th), _out,
-                                                    C.byref(_flag), L.dptr(_each), C.byref(_nused)))
-            _drifts = [_each[_i].copy() for _i in range(_nused.value)]
-            if verbose:
-                for _i, _dft in enumerate(_drifts):
-                    print(f"-- drift {_i}: {np.around(_dft, 2)}")
-                print(f"-- {len(_drifts)} crops in {time.time()-_start_time:.3f}s.")
-            if _flag.value == 0:
-                _updated_mean_dft = np.array([_out[0], _out[1], _out[2]])
+            if len(_cl) > MAX_DEVICE_CROPS:
+                # more crops than the library call takes: the same device phase correlation crop by crop, the rule
+                # after every crop here (:664-674)
+                for _i, _c in enumerate(_cl):
+                    _crop_time = time.time()
+                    _sim, _rim = _src.crop(_c), _ref.crop(_c)
+                    try:
+                        _dft = phase_cross_correlation(_rim, _sim, upsample_factor=precision_fold,
+                                                       normalization=DEFAULT_NORMALIZATION)[0]
+                    finally:
+                        _sim.free()
+                        _rim.free()
+                    _drifts.append(_dft)
+                    if verbose:
+                        print(f"-- drift {_i}: {np.around(_dft, 2)} in {time.time()-_crop_time:.3f}s.")
+                    _updated_mean_dft, _agree = _consensus_drift(_drifts, min_good_drifts, drift_diff_th)
+                    if _updated_mean_dft is not None:
+                        if verbose:
+                            print(f"--- crops {_agree} agree within {drift_diff_th} px: done.")
+                        break
                 if verbose:
-                    print(f"--- crops agree within {drift_diff_th} px: done.")
+                    print(f"-- {len(_drifts)} crops in {time.time()-_start_time:.3f}s.")
+            else:
+                _out, _flag, _nused = (C.c_double * 3)(), C.c_int(0), C.c_int(0)
+                _each = np.zeros((len(_cl), 3), dtype=np.float64)
+                if _dref is not None:
+                    L.check(L.lib().ia3_align_image_ref(_src._h, _dref._h, int(precision_fold),
+                                                        1 if DEFAULT_NORMALIZATION == "phase" else 0, int(min_good_drifts),
+                                                        float(drift_diff_th), _out, C.byref(_flag), L.dptr(_each),
+                                                        C.byref(_nused)))
+                else:
+                    L.check(L.lib().ia3_align_image_dev(_src._h, _ref._h, L.ptr(_cl), len(_cl),
+                                                        int(precision_fold), 1 if DEFAULT_NORMALIZATION == "phase" else 0,
+                                                        int(min_good_drifts), float(drift_diff_th), _out,
+                                                        C.byref(_flag), L.dptr(_each), C.byref(_nused)))
+                _drifts = [_each[_i].copy() for _i in range(_nused.value)]
+                if verbose:
+                    for _i, _dft in enumerate(_drifts):
+                        print(f"-- drift {_i}: {np.around(_dft, 2)}")
+                    print(f"-- {len(_drifts)} crops in {time.time()-_start_time:.3f}s.")
+                if _flag.value == 0:
+                    _updated_mean_dft = np.array([_out[0], _out[1], _out[2]])
+                    if verbose:
+                        print(f"--- crops agree within {drift_diff_th} px: done.")
         for _i, _crop in enumerate(crop_list if not use_autocorr else []):
             _start_time = time.time()
             _lims = np.array(_crop, dtype=int)

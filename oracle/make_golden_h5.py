@@ -8,6 +8,10 @@ interpreter has it, so this script runs the REFERENCE's own functions there:
 and writes tests/golden/h5batch.npz (+ tests/golden/fov_ref.hdf5, a small save file produced by h5py and the reference's
 helpers, which the h5lite tests read back).  The save-file group itself is created with the h5py calls of
 classes/field_of_view.py:1340-1398 (ids / channels / ims / spots / raw_spots / drifts / flags).
+
+The same interpreter has scikit-image 0.18.3; two more arguments record what it and the reference's align_image answer:
+`phase` -> tests/golden/phase.npz (phase_golden), `phase_edges` -> tests/golden/phase_edges.npz (phase_edges_golden: the
+cases of tests/align_edge_cases.py).  Each writes its own file and no other.
 """
 import contextlib
 import io
@@ -160,9 +164,47 @@ def phase_golden():
         print(k, d[k])
 
 
+def phase_edges_golden():
+    """The same two real functions off the friendly sizes (tests/align_edge_cases.py holds the cases): odd and unit
+    axes, rows shorter than 8, sizes off the matrix-core tiles, upsample factors 1 .. 100, whole-voxel rolls up to and
+    past half an axis, and align_image's crop loop with odd, unequal, clipped, few and more than eight crops, every
+    first-batch size and a rule that is met by the fourth crop.  Results only; phase.npz is not touched."""
+    import skimage
+    from skimage.registration import phase_cross_correlation
+    import align_edge_cases as E
+    R = ref_loader.load_reference()
+    d = {"skimage_version": np.array(skimage.__version__)}
+
+    def rec(a, b, up):
+        sh, err, ph = phase_cross_correlation(a, b, upsample_factor=up)
+        return np.concatenate([np.asarray(sh, np.float64), [err, ph]])
+    for name in E.PCC_CASES:
+        for tag, dt in E.DTYPES:
+            a, b = E.pcc_pair(name, dt)
+            for up in E.UPSAMPLES:
+                d[E.pcc_key(name, tag, up)] = rec(a, b, up)
+    for name in E.ROLL_CASES:
+        for k in range(len(E.ROLL_CASES[name][4])):
+            for tag, dt in E.DTYPES:
+                a, b = E.roll_pair(name, k, dt)
+                for up in E.ROLL_UPSAMPLES:
+                    d[E.roll_key(name, k, tag, up)] = rec(a, b, up)
+    for name, (image, crops, kw) in E.align_cases().items():
+        for tag, dt in E.DTYPES:
+            src, ref = E.align_images(image, dt)
+            out = quiet(R.alignment.align_image, src, ref, crop_list=crops, use_autocorr=True, verbose=False, **kw)
+            d[E.align_key(name, tag)] = np.concatenate([np.asarray(out[0], np.float64), [float(out[1])]])
+    np.savez_compressed(os.path.join(OUT, "phase_edges.npz"), **d)
+    for k in sorted(d):
+        print(k, d[k])
+
+
 if __name__ == "__main__":
     if len(sys.argv) > 1 and sys.argv[1] == "phase":
         phase_golden()
+        sys.exit(0)
+    if len(sys.argv) > 1 and sys.argv[1] == "phase_edges":
+        phase_edges_golden()
         sys.exit(0)
     B = ref_loader.load_batch()
     d = {}
