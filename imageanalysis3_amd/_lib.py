@@ -30,6 +30,10 @@ IA3_DENSITY_MAX_CELL = 65536                        # loci of one cell of a Dens
 IA3_MOVIE_MAXCH = 8
 IA3_CLOUD_F64, IA3_CLOUD_F32 = 0, 1                 # ia3_cloud_render modes
 IA3_CLOUD_MAX_S, IA3_CLOUD_MAX_KER_S, IA3_CLOUD_MAX_IMAGES, IA3_CLOUD_MAX_DIM = 4096, 511, 65535, 4096
+IA3_DOMAIN_MAX_WINDOW, IA3_DOMAIN_MAX_WINDOWS, IA3_DOMAIN_MAX_R = 16, 16, 16384   # window size, sizes per call, loci of a copy
+(IA3_DOMAIN_WINDOW_MEDIAN, IA3_DOMAIN_WINDOW_MEAN, IA3_DOMAIN_WINDOW_KS, IA3_DOMAIN_WINDOW_NORMED_INSULATION,
+ IA3_DOMAIN_WINDOW_INSULATION) = range(5)
+IA3_DOMAIN_DIST_MEDIAN, IA3_DOMAIN_DIST_ABSOLUTE_MEDIAN, IA3_DOMAIN_DIST_INSULATION = range(3)
 # the names this module gave some of them before
 MODE_REFLECT, MODE_NEAREST, MODE_CONSTANT = IA3_MODE_REFLECT, IA3_MODE_NEAREST, IA3_MODE_CONSTANT
 BLUR_DIVIDE, BLUR_SUBTRACT, BLUR_MAX_GB = IA3_BLUR_DIVIDE, IA3_BLUR_SUBTRACT, IA3_BLUR_MAX_GB
@@ -290,6 +294,12 @@ PROTOTYPES = {
     "ia3_cloud_render_dev": (_I, [_DP, _IP, _I, _I, _I, _I, _I, _I, _H]),
     "ia3_cloud_render": (_I, [_DP, _IP, _I, _I, _I, _I, _I, _H, _H]),
     "ia3_cloud_gauss_ker": (_I, [_DP, _I, _DP, _DP]),
+    # domain distances of traced chromosomes
+    "ia3_domain_create": (_I, [_DP, _I, _I, _I, _DP, _H]),
+    "ia3_domain_free": (None, [_H]),
+    "ia3_domain_slide_dev": (_I, [_H, _IP, _I, _I, _I, _DP]),
+    "ia3_domain_dists_dev": (_I, [_H, _IP, _I, _I, _I, _I, _DP, _IP]),
+    "ia3_domain_contacts_dev": (_I, [_H, _IP, _I, _D, _DP, _IP]),
     # whole round-folder movies
     "ia3_process_movies": (_I, [_MOVJ, _I, _MOVP]),
 }
@@ -1619,3 +1629,144 @@ def cloud_gauss_ker(sig, s, disp):
     out = np.empty((s + 1,) * 3, dtype=np.float64)
     check(lib().ia3_cloud_gauss_ker(ptr(sig), s, ptr(disp), ptr(out)))
     return out
+
+
+# ---- domain distances of traced chromosomes (csrc/domain.hip) -----------------------------------------------------------------
+DOMAIN_WINDOW_METRICS = {'median': IA3_DOMAIN_WINDOW_MEDIAN, 'mean': IA3_DOMAIN_WINDOW_MEAN, 'ks': IA3_DOMAIN_WINDOW_KS,
+                         'normed_insulation': IA3_DOMAIN_WINDOW_NORMED_INSULATION, 'insulation': IA3_DOMAIN_WINDOW_INSULATION}
+DOMAIN_DIST_METRICS = {'median': IA3_DOMAIN_DIST_MEDIAN, 'absolute_median': IA3_DOMAIN_DIST_ABSOLUTE_MEDIAN,
+                       'insulation': IA3_DOMAIN_DIST_INSULATION}
+
+
+def domain_rows(R):
+    """The number of loci of a copy: ValueError below 1, NotImplementedError above IA3_DOMAIN_MAX_R."""
+    R = int(R)
+    if R < 1:
+        raise ValueError("domain distances: a chromosome of %d loci" % R)
+    if R > IA3_DOMAIN_MAX_R:
+        raise NotImplementedError("domain distances: %d loci (at most %d are built: a quadruple's entries are counted in "
+                                  "32 bits and a distance map is one allocation)" % (R, IA3_DOMAIN_MAX_R))
+    return R
+
+
+def domain_normalization(normalization, R):
+    """The (R, R) float64 normalisation map, or None.  ValueError for another shape and, with the words of
+    scipy.spatial.distance.squareform (which the reference runs on its diagonal blocks), for a map that is not symmetric
+    or whose diagonal is not zero."""
+    if normalization is None:
+        return None
+    m = np.ascontiguousarray(normalization, dtype=np.float64)
+    if m.shape != (R, R):
+        raise ValueError("Wrong shape of normalization:%s, should be equal to %s" % (m.shape, (R, R)))
+    if not (m == m.T).all():
+        raise ValueError("Distance matrix 'X' must be symmetric.")
+    if not (m[np.diag_indices(R)] == 0).all():
+        raise ValueError("Distance matrix 'X' diagonal must be zero.")
+    return m
+
+
+def domain_window_sizes(window_sizes):
+    """1 to IA3_DOMAIN_MAX_WINDOWS window sizes as int32 (``int(wd)`` each): ValueError for none, too many or one below 1,
+    NotImplementedError for one above IA3_DOMAIN_MAX_WINDOW."""
+    wds = np.array([int(w) for w in np.atleast_1d(window_sizes)], dtype=np.int64)
+    if wds.ndim != 1 or len(wds) < 1 or len(wds) > IA3_DOMAIN_MAX_WINDOWS:
+        raise ValueError("sliding windows: %d window sizes (1 to %d per call)" % (wds.size, IA3_DOMAIN_MAX_WINDOWS))
+    if wds.min() < 1:
+        raise ValueError("sliding windows: window size %d" % wds.min())
+    if wds.max() > IA3_DOMAIN_MAX_WINDOW:
+        raise NotImplementedError("sliding windows: window size %d (at most %d is built: a wavefront keeps the two sets of a "
+                                  "window in LDS)" % (wds.max(), IA3_DOMAIN_MAX_WINDOW))
+    return wds.astype(np.int32)
+
+
+def domain_quads(quads, N, R):
+    """(Q, 5) int32 entries (copy, s1, e1, s2, e2) of a population of N copies x R loci: ValueError for another shape, no
+    entry, a copy outside 0..N-1 and bounds that are not 0 <= s <= e <= R (a slice the reference would clip or wrap)."""
+    q = np.asarray(quads)
+    if q.ndim != 2 or q.shape[1] != 5 or len(q) < 1:
+        raise ValueError("domain entries: a (Q, 5) table of (copy, s1, e1, s2, e2) with Q >= 1 is required, got shape %s" % (q.shape,))
+    q = q.astype(np.int64)
+    if q[:, 0].min() < 0 or q[:, 0].max() >= N:
+        raise ValueError("domain entries: a copy outside 0..%d" % (N - 1))
+    if q[:, 1:].min() < 0 or q[:, 1:].max() > R or (q[:, 2] < q[:, 1]).any() or (q[:, 4] < q[:, 3]).any():
+        raise ValueError("domain entries: bounds that are not 0 <= start <= end <= %d" % R)
+    return np.ascontiguousarray(q, dtype=np.int32)
+
+
+class DomainPopulation(Owner):
+    """N chromosome copies x R loci resident in HBM (owner of an ``ia3_domain_create`` handle): their (N, R, 3) float64
+    coordinates, NaN for a missing locus, or one (R, R) distance map (N = 1); optionally one (R, R) normalisation map shared
+    by all copies.  ``slide``, ``distances`` and ``contacts`` are the three kernels of domain_tools/distance.py."""
+
+    def __init__(self, handle, N, R, is_matrix, has_norm):
+        self._h = handle
+        self.N, self.R, self.is_matrix, self.has_norm = N, R, is_matrix, has_norm
+
+    @classmethod
+    def _create(cls, data, N, R, is_matrix, normalization):
+        norm = domain_normalization(normalization, R)
+        h = C.c_void_p()
+        check(lib().ia3_domain_create(ptr(data.reshape(-1)), N, R, 1 if is_matrix else 0, None if norm is None else ptr(norm.reshape(-1)),
+                                      C.byref(h)))
+        return cls(h, N, R, is_matrix, norm is not None)
+
+    @classmethod
+    def upload(cls, zxys, normalization=None):
+        """``zxys``: (N, R, 3) coordinates, or (R, 3) for one copy."""
+        a = np.ascontiguousarray(zxys, dtype=np.float64)
+        if a.ndim == 2:
+            a = a[None]
+        if a.ndim != 3 or a.shape[2] != 3 or a.shape[0] < 1:
+            raise ValueError("DomainPopulation.upload: (N, R, 3) coordinates are required, got shape %s" % (a.shape,))
+        return cls._create(a, a.shape[0], domain_rows(a.shape[1]), False, normalization)
+
+    @classmethod
+    def upload_matrix(cls, mat, normalization=None):
+        """``mat``: one (R, R) distance map; entry [i, j] is the distance the reference reads as ``_mat[i, j]``."""
+        a = np.ascontiguousarray(mat, dtype=np.float64)
+        if a.ndim != 2 or a.shape[0] != a.shape[1]:
+            raise ValueError("DomainPopulation.upload_matrix: an (R, R) distance map is required, got shape %s" % (a.shape,))
+        return cls._create(a, 1, domain_rows(a.shape[0]), True, normalization)
+
+    def _use_norm(self, normalize):
+        if normalize is None:
+            return 1 if self.has_norm else 0
+        if normalize and not self.has_norm:
+            raise ValueError("DomainPopulation: the population holds no normalisation map")
+        return 1 if normalize else 0
+
+    def slide(self, window_sizes, metric='median', normalize=False):
+        """``ia3_domain_slide_dev``: the (N, W, R) float64 sliding-window distances of every copy."""
+        wds = domain_window_sizes(window_sizes)
+        if metric not in DOMAIN_WINDOW_METRICS:
+            raise ValueError(f"Wrong input _dist_metric")
+        use_norm = self._use_norm(normalize)
+        out = np.empty((self.N, len(wds), self.R), dtype=np.float64)
+        check(lib().ia3_domain_slide_dev(self._h, ptr(wds), len(wds), DOMAIN_WINDOW_METRICS[metric], use_norm, ptr(out.reshape(-1))))
+        return out
+
+    def distances(self, quads, metric='median', allow_minus=True, normalize=None):
+        """``ia3_domain_dists_dev``: (values (Q,) float64, int_zero (Q,) bool) of the (Q, 5) entries (copy, s1, e1, s2, e2);
+        ``int_zero`` marks where the reference returns Python's integer 0.  ``normalize`` None: divide when the population
+        holds a normalisation map."""
+        q = domain_quads(quads, self.N, self.R)
+        if metric not in DOMAIN_DIST_METRICS:
+            raise ValueError("Wrong input _metric type:%s" % (metric,))
+        use_norm = self._use_norm(normalize)
+        out = np.empty(len(q), dtype=np.float64)
+        flag = np.empty(len(q), dtype=np.int32)
+        check(lib().ia3_domain_dists_dev(self._h, ptr(q.reshape(-1)), len(q), DOMAIN_DIST_METRICS[metric], 1 if allow_minus else 0,
+                                         use_norm, ptr(out), ptr(flag)))
+        return out, flag != 0
+
+    def contacts(self, quads, contact_th=400, return_counts=False):
+        """``ia3_domain_contacts_dev``: per entry the share of the block [s1:e1, s2:e2] that is <= ``contact_th``; with
+        ``return_counts`` also the int32 counts."""
+        q = domain_quads(quads, self.N, self.R)
+        freq = np.empty(len(q), dtype=np.float64)
+        cnt = np.empty(len(q), dtype=np.int32)
+        check(lib().ia3_domain_contacts_dev(self._h, ptr(q.reshape(-1)), len(q), float(contact_th), ptr(freq), ptr(cnt)))
+        return (freq, cnt) if return_counts else freq
+
+    def _release(self, handle):
+        lib().ia3_domain_free(handle)

@@ -889,6 +889,43 @@ int ia3_cloud_render(const double* sources, const int* image_start, int n_images
                      const void* init, void* out);
 int ia3_cloud_gauss_ker(const double* sig, int s, const double* disp, double* out);
 
+/* ---- domain distances of traced chromosomes: domain_tools/distance.py (csrc/domain.hip) ------------
+ * ia3_domain_create uploads a population once: N copies x R loci of (z, x, y) float64 coordinates, NaN for a missing locus
+ * (is_matrix 0), or ONE R x R float64 distance map (is_matrix 1, N must be 1); `norm` is NULL or one R x R float64
+ * normalisation map shared by all copies (the caller has checked that it is symmetric with a zero diagonal).  A distance
+ * d[r, c] is sqrt((dz*dz + dx*dx) + dy*dy) of loci r and c (scipy's pdist / cdist arithmetic) or entry [r, c] of the map,
+ * divided by norm[r, c] where a call sets use_norm.  Host pointers in, host pointers out; each call waits once.
+ *   ia3_domain_slide_dev     _sliding_window_dist (:19-67) of every copy for W window sizes (1 .. IA3_DOMAIN_MAX_WINDOW each,
+ *                            W <= IA3_DOMAIN_MAX_WINDOWS): out is (N, W, R) float64.  For coordinates the map is
+ *                            squareform(pdist(zxy)).  Equal to the reference in every bit; where it gives NaN, a NaN.
+ *   ia3_domain_dists_dev     domain_distance (:69-158) for Q entries (copy, s1, e1, s2, e2) of int32: the two domains are the
+ *                            loci [s1, e1) and [s2, e2).  metric IA3_DOMAIN_DIST_*; int_zero[q] is 1 where Python returns
+ *                            the integer 0 (a set without a value that is not NaN, or max(_final_dist, 0) took the 0) and
+ *                            out[q] is then 0.
+ *   ia3_domain_contacts_dev  one block of _domain_contact_freq (:465-490) per entry: n_contact[q] (optional) entries of
+ *                            d[s1:e1, s2:e2] are <= contact_th, freq[q] is that count over the block's size (0 / 0: NaN);
+ *                            for coordinates d is squareform(pdist(zxy)), diagonal 0.  A NaN is never a contact.
+ * IA3_EINVAL before any launch: a null pointer, Q < 1, an entry whose copy or bounds lie outside the population
+ * (0 <= s <= e <= R), a metric outside its list, a window size < 1, use_norm without a map.  IA3_EUNSUPPORTED: R above
+ * IA3_DOMAIN_MAX_R, a window size above IA3_DOMAIN_MAX_WINDOW, more than 2^31 - 1 windows in one call. */
+#define IA3_DOMAIN_MAX_WINDOW 16
+#define IA3_DOMAIN_MAX_WINDOWS 16
+#define IA3_DOMAIN_MAX_R 16384
+#define IA3_DOMAIN_WINDOW_MEDIAN 0
+#define IA3_DOMAIN_WINDOW_MEAN 1
+#define IA3_DOMAIN_WINDOW_KS 2
+#define IA3_DOMAIN_WINDOW_NORMED_INSULATION 3
+#define IA3_DOMAIN_WINDOW_INSULATION 4
+#define IA3_DOMAIN_DIST_MEDIAN 0
+#define IA3_DOMAIN_DIST_ABSOLUTE_MEDIAN 1
+#define IA3_DOMAIN_DIST_INSULATION 2
+int ia3_domain_create(const double* data, int N, int R, int is_matrix, const double* norm, void** out);
+void ia3_domain_free(void* population);
+int ia3_domain_slide_dev(void* population, const int* window_sizes, int W, int metric, int use_norm, double* out);
+int ia3_domain_dists_dev(void* population, const int* quads, int Q, int metric, int allow_minus, int use_norm, double* out,
+                         int* int_zero);
+int ia3_domain_contacts_dev(void* population, const int* quads, int Q, double contact_th, double* freq, int* n_contact);
+
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
  * Per movie: raw (frames, X, Y) uint16 movie from host memory or a .dax file -> split_im_by_channels
