@@ -34,6 +34,10 @@ IA3_DOMAIN_MAX_WINDOW, IA3_DOMAIN_MAX_WINDOWS, IA3_DOMAIN_MAX_R = 16, 16, 16384 
 (IA3_DOMAIN_WINDOW_MEDIAN, IA3_DOMAIN_WINDOW_MEAN, IA3_DOMAIN_WINDOW_KS, IA3_DOMAIN_WINDOW_NORMED_INSULATION,
  IA3_DOMAIN_WINDOW_INSULATION) = range(5)
 IA3_DOMAIN_DIST_MEDIAN, IA3_DOMAIN_DIST_ABSOLUTE_MEDIAN, IA3_DOMAIN_DIST_INSULATION = range(3)
+IA3_SCORE_MAX_PER_REGION, IA3_SCORE_MAX_LOCAL = 64, 33   # rows of one region id in a chromosome, local_size
+(IA3_SCORE_KIND_DIST_LINEAR, IA3_SCORE_KIND_DIST_CDF, IA3_SCORE_KIND_INT_LINEAR, IA3_SCORE_KIND_INT_CDF,
+ IA3_SCORE_KIND_CUM_PROB) = range(5)
+IA3_SCORE_REF_MEDIAN, IA3_SCORE_REF_MEAN, IA3_SCORE_REF_RG, IA3_SCORE_REF_CDF = range(4)
 # the names this module gave some of them before
 MODE_REFLECT, MODE_NEAREST, MODE_CONSTANT = IA3_MODE_REFLECT, IA3_MODE_NEAREST, IA3_MODE_CONSTANT
 BLUR_DIVIDE, BLUR_SUBTRACT, BLUR_MAX_GB = IA3_BLUR_DIVIDE, IA3_BLUR_SUBTRACT, IA3_BLUR_MAX_GB
@@ -300,6 +304,14 @@ PROTOTYPES = {
     "ia3_domain_slide_dev": (_I, [_H, _IP, _I, _I, _I, _DP]),
     "ia3_domain_dists_dev": (_I, [_H, _IP, _I, _I, _I, _I, _DP, _IP]),
     "ia3_domain_contacts_dev": (_I, [_H, _IP, _I, _D, _DP, _IP]),
+    # chromosomal spot scores
+    "ia3_score_create": (_I, [_DP, _LP, _IP, _DP, _LP, _IP, _DP, _IP, _I, _DP, _H]),
+    "ia3_score_replace_selected": (_I, [_H, _DP, _LP, _IP]),
+    "ia3_score_free": (None, [_H]),
+    "ia3_score_refs_dev": (_I, [_H, _I, _I, _D, _I, _DP, _IP, _DP]),
+    "ia3_score_scores_dev": (_I, [_H, _I, _I, _I, _LL, _D, _D, _I, _DP, _D, _D, _DP, _DP, _BP, _IP]),
+    "ia3_score_values_dev": (_I, [_DP, _I, _D, _DP, _I, _I, _D, _D, _D, _DP, _BP, _IP]),
+    "ia3_score_neighbor_lists_dev": (_I, [_H, _LL, _D, _IP, _IP, _DP, _DP]),
     # whole round-folder movies
     "ia3_process_movies": (_I, [_MOVJ, _I, _MOVP]),
 }
@@ -1770,3 +1782,206 @@ class DomainPopulation(Owner):
 
     def _release(self, handle):
         lib().ia3_domain_free(handle)
+
+
+# ---- chromosomal spot scores (csrc/score.hip) ---------------------------------------------------------------------------------
+SCORE_REF_METRICS = {'median': IA3_SCORE_REF_MEDIAN, 'mean': IA3_SCORE_REF_MEAN, 'rg': IA3_SCORE_REF_RG, 'cdf': IA3_SCORE_REF_CDF}
+SCORE_VALUE, SCORE_LOG, SCORE_NEG_INF, SCORE_NAN_IN = 0, 1, 2, 4   # the class byte of a value (ia3_score_scores_dev)
+_SCORE_CDF_KINDS = (IA3_SCORE_KIND_DIST_CDF, IA3_SCORE_KIND_INT_CDF, IA3_SCORE_KIND_CUM_PROB)
+
+
+def score_half(local_size):
+    """``int((local_size - 1) / 2)`` of _local_distance: IndexError below 0 (np.delete of an empty range, as in the
+    reference), NotImplementedError above what IA3_SCORE_MAX_LOCAL gives."""
+    half = int((local_size - 1) / 2)
+    if half < 0:
+        raise IndexError("index %d is out of bounds for axis 0 with size 0" % half)
+    if half > (IA3_SCORE_MAX_LOCAL - 1) // 2:
+        raise NotImplementedError("spot scores: local_size %s (at most %d is built: a spot gathers the rows of at most %d "
+                                  "neighbouring regions)" % (local_size, IA3_SCORE_MAX_LOCAL, IA3_SCORE_MAX_LOCAL - 1))
+    return half
+
+
+def score_step(neighbor_step):
+    step = int(neighbor_step)
+    if abs(step) > 2**31 - 1:
+        raise ValueError("spot scores: neighbor_step %d" % step)
+    return step
+
+
+def score_table(rows_list, ids_list, what):
+    """The CSR form of one table: ((n, 4) float64 rows (h, z, x, y), (n,) int64 region ids, (C + 1,) int32 offsets).
+    ``ids_list[c]`` None: 0 .. len - 1.  IndexError for rows that are not 2-D with four columns or more or whose ids differ
+    in number, ValueError for no chromosome, a chromosome without a row and an id outside int32, NotImplementedError for
+    more than IA3_SCORE_MAX_PER_REGION rows of one region id in a chromosome."""
+    rows_list = list(rows_list)
+    ids_list = [None] * len(rows_list) if ids_list is None else list(ids_list)
+    if len(rows_list) < 1 or len(ids_list) != len(rows_list):
+        raise ValueError("spot scores: %d %s tables with %d lists of ids" % (len(rows_list), what, len(ids_list)))
+    rows, ids, start = [], [], [0]
+    for c, (r, i) in enumerate(zip(rows_list, ids_list)):
+        r = np.asarray(r, dtype=np.float64)
+        if r.ndim != 2 or r.shape[1] < 4:
+            raise IndexError("Wrong shape of %s spots of chromosome %d, should be 2d array of (h, z, x, y, ...) rows, got %s" % (what, c, r.shape))
+        i = np.arange(len(r), dtype=np.int64) if i is None else np.asarray(i)
+        if i.ndim != 1 or len(i) != len(r):
+            raise IndexError("Wrong input length of %s spots and ids of chromosome %d, length should match!" % (what, c))
+        if len(r) < 1:
+            raise ValueError("spot scores: chromosome %d has no %s spot" % (c, what))
+        if i.dtype.kind == 'f' and not np.isfinite(i).all():
+            raise ValueError("spot scores: a region id of chromosome %d is not a number" % c)
+        i = i.astype(np.int64)
+        if i.min() < -2**31 or i.max() > 2**31 - 1:
+            raise ValueError("spot scores: a region id of chromosome %d lies outside int32" % c)
+        most = int(np.unique(i, return_counts=True)[1].max())
+        if most > IA3_SCORE_MAX_PER_REGION:
+            raise NotImplementedError("spot scores: %d %s spots of one region in chromosome %d (at most %d are built: a median is "
+                                      "ranked within one wavefront)" % (most, what, c, IA3_SCORE_MAX_PER_REGION))
+        rows.append(r[:, :4])
+        ids.append(i)
+        start.append(start[-1] + len(r))
+    if start[-1] > 2**31 - 1:
+        raise NotImplementedError("spot scores: %d %s rows in one population" % (start[-1], what))
+    return np.ascontiguousarray(np.concatenate(rows)), np.ascontiguousarray(np.concatenate(ids)), np.array(start, dtype=np.int32)
+
+
+def score_values(x, kind, ref_array=None, ref_scalar=0.0, weight=1.0, limit_lo=-np.inf, limit_hi=np.inf):
+    """``ia3_score_values_dev``: (values, class bytes, number of reference values that are not NaN) for the 1-D float64 ``x``
+    against one reference: ``ref_array`` for the cdf kinds, ``ref_scalar`` for the linear ones."""
+    x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+    val = np.empty(len(x), dtype=np.float64)
+    cls = np.empty(len(x), dtype=np.uint8)
+    cnt = np.zeros(1, dtype=np.int32)
+    if len(x) == 0:
+        return val, cls, 0
+    ref = None
+    if kind in _SCORE_CDF_KINDS:
+        ref = np.ascontiguousarray(ref_array, dtype=np.float64).reshape(-1)
+        if len(ref) < 1:
+            raise ValueError("spot scores: an empty reference array")
+    check(lib().ia3_score_values_dev(None if ref is None else ptr(ref), 0 if ref is None else len(ref), float(ref_scalar), ptr(x), len(x), int(kind),
+                                     float(weight), float(limit_lo), float(limit_hi), ptr(val), ptr(cls), ptr(cnt)))
+    return val, cls, int(cnt[0])
+
+
+class ScorePopulation(Owner):
+    """C traced chromosomes resident in HBM (owner of an ``ia3_score_create`` handle): per chromosome its candidate spots and
+    its currently selected spots, (h, z, x, y) rows in pixels with a region id each, optionally a centre in pixels, and the
+    pixel sizes.  ``replace_selected`` swaps the selected spots, which is all an EM iteration of the per-cell pickers
+    changes."""
+
+    def __init__(self, handle, cand_ids, cand_start, sel_start):
+        self._h = handle
+        self.cand_ids, self.cand_start, self.sel_start = cand_ids, cand_start, sel_start
+        self.C, self.N, self.S = len(cand_start) - 1, int(cand_start[-1]), int(sel_start[-1])
+
+    @classmethod
+    def upload(cls, cand_spots, cand_ids, sel_spots, sel_ids=None, chr_centers=None, distance_zxy=(200, 108, 108)):
+        """Lists of C tables each; ``chr_centers``: None, or a list of C entries, each None or a (z, x, y) centre in pixels."""
+        cand, cid, cstart = score_table(cand_spots, cand_ids, "candidate")
+        sel, sid, sstart = score_table(sel_spots, sel_ids, "selected")
+        n_chrom = len(cstart) - 1
+        if len(sstart) - 1 != n_chrom:
+            raise ValueError("spot scores: %d candidate tables and %d selected tables" % (n_chrom, len(sstart) - 1))
+        dz = np.ascontiguousarray(distance_zxy, dtype=np.float64).reshape(-1)
+        if len(dz) != 3:
+            raise ValueError("spot scores: distance_zxy of %d values" % len(dz))
+        centers, has = None, None
+        if chr_centers is not None:
+            chr_centers = list(chr_centers)
+            if len(chr_centers) != n_chrom:
+                raise ValueError("spot scores: %d centres for %d chromosomes" % (len(chr_centers), n_chrom))
+            centers, has = np.zeros((n_chrom, 3)), np.zeros(n_chrom, dtype=np.int32)
+            for c, ctr in enumerate(chr_centers):
+                if ctr is not None:
+                    centers[c] = np.asarray(ctr, dtype=np.float64).reshape(3)
+                    has[c] = 1
+        h = C.c_void_p()
+        check(lib().ia3_score_create(ptr(cand.reshape(-1)), ptr(cid), ptr(cstart), ptr(sel.reshape(-1)), ptr(sid), ptr(sstart),
+                                     None if centers is None else ptr(centers.reshape(-1)), None if has is None else ptr(has), n_chrom, ptr(dz),
+                                     C.byref(h)))
+        return cls(h, cid, cstart, sstart)
+
+    def replace_selected(self, sel_spots, sel_ids=None):
+        sel, sid, sstart = score_table(sel_spots, sel_ids, "selected")
+        if len(sstart) - 1 != self.C:
+            raise ValueError("spot scores: %d selected tables for %d chromosomes" % (len(sstart) - 1, self.C))
+        check(lib().ia3_score_replace_selected(self._h, ptr(sel.reshape(-1)), ptr(sid), ptr(sstart)))
+        self.sel_start, self.S = sstart, int(sstart[-1])
+
+    @staticmethod
+    def _ref_metric(ref_metric):
+        m = str(ref_metric).lower()
+        if m not in SCORE_REF_METRICS:
+            raise ValueError(f"Not supported yet!")
+        return SCORE_REF_METRICS[m]
+
+    def references(self, ref_metric='median', local_size=5, intensity_th=0., ignore_nan=True):
+        """``ia3_score_refs_dev``: (arrays, counts (C, 4), scalars (C, 4)); ``arrays[c][a]`` is what the reference keeps of the
+        centre, local and neighbour distances and the intensities of chromosome c (with ``ignore_nan`` without NaNs, the
+        fallback value where nothing is left: its count is -1)."""
+        metric, half = self._ref_metric(ref_metric), score_half(local_size)
+        arrays = np.empty((4, self.S), dtype=np.float64)
+        counts = np.empty((self.C, 4), dtype=np.int32)
+        scalars = np.empty((self.C, 4), dtype=np.float64)
+        check(lib().ia3_score_refs_dev(self._h, metric, half, float(intensity_th), 1 if ignore_nan else 0, ptr(arrays.reshape(-1)),
+                                       ptr(counts.reshape(-1)), ptr(scalars.reshape(-1))))
+        s = self.sel_start
+        return [[arrays[a, s[c]:s[c] + abs(counts[c, a])].copy() for a in range(4)] for c in range(self.C)], counts, scalars
+
+    def geometry(self, local_size=5, neighbor_step=1, invalid_dist=np.nan):
+        """(5, N) float64: the centre, local, forward, reverse and mean neighbour distance of every candidate."""
+        half, step = score_half(local_size), score_step(neighbor_step)
+        geom = np.empty((5, self.N), dtype=np.float64)
+        check(lib().ia3_score_scores_dev(self._h, -1, 0, half, step, float(invalid_dist), 0., 1, None, 0., 0., ptr(geom.reshape(-1)), None, None, None))
+        return geom
+
+    def scores(self, score_metric='cdf', ref_metric=None, local_size=5, intensity_th=0., ignore_nan=True, weights=(1., 1., 1., 1.),
+               distance_limits=(0, np.inf)):
+        """``ia3_score_scores_dev``: (values (4, N), class bytes (4, N), reference counts (C, 4)) of the centre, local,
+        neighbour and intensity score of every candidate, up to the argument of np.log."""
+        score_metric = str(score_metric).lower()
+        if score_metric not in ('linear', 'cdf'):
+            raise ValueError(f"metric type:{score_metric} has not been supported yet!")
+        kind = IA3_SCORE_KIND_DIST_CDF if score_metric == 'cdf' else IA3_SCORE_KIND_DIST_LINEAR
+        metric = self._ref_metric(score_metric if ref_metric is None else ref_metric)
+        if (metric == IA3_SCORE_REF_CDF) != (score_metric == 'cdf'):
+            raise ValueError("spot scores: the %s metric with %s references" % (score_metric, ref_metric))
+        half = score_half(local_size)
+        w = np.ascontiguousarray([float(v) for v in weights], dtype=np.float64)
+        if len(w) != 4:
+            raise ValueError("spot scores: %d weights" % len(w))
+        lo, hi = float(min(distance_limits)), float(max(distance_limits))
+        val = np.empty((4, self.N), dtype=np.float64)
+        cls = np.empty((4, self.N), dtype=np.uint8)
+        cnt = np.empty((self.C, 4), dtype=np.int32)
+        check(lib().ia3_score_scores_dev(self._h, kind, metric, half, 1, float('nan'), float(intensity_th), 1 if ignore_nan else 0, ptr(w), lo, hi,
+                                         None, ptr(val.reshape(-1)), ptr(cls.reshape(-1)), ptr(cnt.reshape(-1))))
+        return val, cls, cnt
+
+    def neighbor_lists(self, neighbor_step=1, invalid_dist=np.nan):
+        """neighboring_distances(use_median=False) of every chromosome: two lists of C float64 vectors (forward, reverse)."""
+        step = score_step(neighbor_step)
+        nf, nr = np.zeros(self.N, dtype=np.int64), np.zeros(self.N, dtype=np.int64)
+        for c in range(self.C):
+            a, b = self.cand_start[c], self.cand_start[c + 1]
+            ids = self.cand_ids[a:b]
+            u, k = np.unique(ids, return_counts=True)
+
+            def count(q):
+                at = np.minimum(np.searchsorted(u, q), len(u) - 1)
+                return np.where(u[at] == q, k[at], 0)
+            f = count(ids + step)
+            nf[a:b] = np.where(f > 0, f, 1)
+            nr[a:b] = np.where(f > 0, count(ids - step), 1)
+        if max(nf.sum(), nr.sum()) > 2**31 - 1:
+            raise NotImplementedError("spot scores: %d neighbour distances in one call" % max(nf.sum(), nr.sum()))
+        of = np.concatenate([[0], np.cumsum(nf)]).astype(np.int32)
+        orv = np.concatenate([[0], np.cumsum(nr)]).astype(np.int32)
+        fwd, rev = np.empty(max(of[-1], 1), dtype=np.float64), np.empty(max(orv[-1], 1), dtype=np.float64)
+        check(lib().ia3_score_neighbor_lists_dev(self._h, step, float(invalid_dist), ptr(of), ptr(orv), ptr(fwd), ptr(rev)))
+        s = self.cand_start
+        return ([fwd[of[s[c]]:of[s[c + 1]]].copy() for c in range(self.C)], [rev[orv[s[c]]:orv[s[c + 1]]].copy() for c in range(self.C)])
+
+    def _release(self, handle):
+        lib().ia3_score_free(handle)

@@ -926,6 +926,63 @@ int ia3_domain_dists_dev(void* population, const int* quads, int Q, int metric, 
                          int* int_zero);
 int ia3_domain_contacts_dev(void* population, const int* quads, int Q, double contact_th, double* freq, int* n_contact);
 
+/* ---- chromosomal spot scores: spot_tools/scoring.py (csrc/score.hip) ------------------------------
+ * ia3_score_create uploads C traced chromosomes once, as CSR: chromosome c owns the candidate rows
+ * cand_start[c] .. cand_start[c + 1] and the selected rows sel_start[c] .. sel_start[c + 1] (at least one of each).  A row
+ * is (h, z, x, y) float64 with the coordinates in pixels, its region id an int64 that must lie in int32.  center: (C, 3)
+ * chromosome centres in pixels, used where has_center[c] is non-zero (either may be null: no centre is given);
+ * distance_zxy: the three pixel sizes.  ia3_score_replace_selected swaps the selected rows (the candidates stay).
+ *   ia3_score_refs_dev   generate_ref_from_chromosome (:217-303) of every chromosome.  half = int((local_size - 1) / 2).
+ *                        arrays (4, S): the centre, local and neighbour distances and the filtered intensities of the S
+ *                        selected rows, chromosome by chromosome; with ignore_nan each chromosome's values are moved
+ *                        to the front of its stretch without their NaNs (in row order) and a stretch left empty holds
+ *                        the reference's fallback value.  counts (C, 4): the values of each stretch, -1 where the
+ *                        one value is that fallback; scalars (C, 4): by
+ *                        ref_metric IA3_SCORE_REF_* the nanmedian, the nanmean or the radius of gyration (not for _CDF;
+ *                        the fourth is not set for _RG).
+ *   ia3_score_scores_dev the four scores of every candidate up to the argument of np.log.  geom (5, N): centre, local,
+ *                        forward, reverse and mean neighbour distance of the N candidates (step / invalid:
+ *                        neighbor_step / invalid_dist of :180).  kind < 0: only those.  Otherwise kind is
+ *                        IA3_SCORE_KIND_DIST_LINEAR or _DIST_CDF, the references are made from the selected rows by
+ *                        ref_metric (IA3_SCORE_REF_CDF with the cdf kind) and val / cls (4, N) hold for the centre,
+ *                        local, neighbour and intensity score a value and what is left to do with it: 0 it is the
+ *                        score, 1 the score is np.log(value) * weight, 2 the score is -inf; 4 is added where the
+ *                        distance or intensity was NaN.  ref_counts (C, 4): the values of each reference without NaNs.
+ *   ia3_score_values_dev the same for n values x against one reference given by the caller: kind IA3_SCORE_KIND_* (also
+ *                        _INT_LINEAR, _INT_CDF and _CUM_PROB, the plain _cum_prob of :81-107); ref_array (n_ref values,
+ *                        NaNs dropped, sorted on the device) for the cdf kinds, ref_scalar for the linear ones.
+ *   ia3_score_neighbor_lists_dev   neighboring_distances with use_median=False: every distance between a candidate and
+ *                        the candidates of region id + step (fwd) and id - step (rev) where id + step is a region,
+ *                        else `invalid` once in both; off_fwd / off_rev (N + 1): where each candidate's values start.
+ * IA3_EINVAL before any launch for null pointers, an empty population or chromosome, row offsets that do not ascend, an
+ * id outside int32, more than IA3_SCORE_MAX_PER_REGION rows of one region id in a chromosome and a half window above
+ * (IA3_SCORE_MAX_LOCAL - 1) / 2. */
+#define IA3_SCORE_MAX_PER_REGION 64
+#define IA3_SCORE_MAX_LOCAL 33
+#define IA3_SCORE_KIND_DIST_LINEAR 0
+#define IA3_SCORE_KIND_DIST_CDF 1
+#define IA3_SCORE_KIND_INT_LINEAR 2
+#define IA3_SCORE_KIND_INT_CDF 3
+#define IA3_SCORE_KIND_CUM_PROB 4
+#define IA3_SCORE_REF_MEDIAN 0
+#define IA3_SCORE_REF_MEAN 1
+#define IA3_SCORE_REF_RG 2
+#define IA3_SCORE_REF_CDF 3
+int ia3_score_create(const double* cand, const long long* cand_id, const int* cand_start, const double* sel,
+                     const long long* sel_id, const int* sel_start, const double* center, const int* has_center, int C,
+                     const double* distance_zxy, void** out);
+int ia3_score_replace_selected(void* population, const double* sel, const long long* sel_id, const int* sel_start);
+void ia3_score_free(void* population);
+int ia3_score_refs_dev(void* population, int ref_metric, int half, double intensity_th, int ignore_nan, double* arrays,
+                       int* counts, double* scalars);
+int ia3_score_scores_dev(void* population, int kind, int ref_metric, int half, long long step, double invalid,
+                         double intensity_th, int ignore_nan, const double* weights, double limit_lo, double limit_hi,
+                         double* geom, double* val, unsigned char* cls, int* ref_counts);
+int ia3_score_values_dev(const double* ref_array, int n_ref, double ref_scalar, const double* x, int n, int kind,
+                         double weight, double limit_lo, double limit_hi, double* val, unsigned char* cls, int* ref_count);
+int ia3_score_neighbor_lists_dev(void* population, long long step, double invalid, const int* off_fwd, const int* off_rev,
+                                 double* fwd, double* rev);
+
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
  * Per movie: raw (frames, X, Y) uint16 movie from host memory or a .dax file -> split_im_by_channels
