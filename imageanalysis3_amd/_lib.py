@@ -38,6 +38,9 @@ IA3_SCORE_MAX_PER_REGION, IA3_SCORE_MAX_LOCAL = 64, 33   # rows of one region id
 (IA3_SCORE_KIND_DIST_LINEAR, IA3_SCORE_KIND_DIST_CDF, IA3_SCORE_KIND_INT_LINEAR, IA3_SCORE_KIND_INT_CDF,
  IA3_SCORE_KIND_CUM_PROB) = range(5)
 IA3_SCORE_REF_MEDIAN, IA3_SCORE_REF_MEAN, IA3_SCORE_REF_RG, IA3_SCORE_REF_CDF = range(4)
+IA3_CELLPICK_MAX_CHROM, IA3_CELLPICK_MAX_SPOTS = 6, 64   # chromosomes of a cell, merged spots of a region
+IA3_CELLPICK_NAIVE_OWN, IA3_CELLPICK_NAIVE_MERGED = 0, 1
+IA3_CELLPICK_MAX_TUPLES = 4194304                        # index tuples one spot of the next region may walk
 # the names this module gave some of them before
 MODE_REFLECT, MODE_NEAREST, MODE_CONSTANT = IA3_MODE_REFLECT, IA3_MODE_NEAREST, IA3_MODE_CONSTANT
 BLUR_DIVIDE, BLUR_SUBTRACT, BLUR_MAX_GB = IA3_BLUR_DIVIDE, IA3_BLUR_SUBTRACT, IA3_BLUR_MAX_GB
@@ -312,6 +315,13 @@ PROTOTYPES = {
     "ia3_score_scores_dev": (_I, [_H, _I, _I, _I, _LL, _D, _D, _I, _DP, _D, _D, _DP, _DP, _BP, _IP]),
     "ia3_score_values_dev": (_I, [_DP, _I, _D, _DP, _I, _I, _D, _D, _D, _DP, _BP, _IP]),
     "ia3_score_neighbor_lists_dev": (_I, [_H, _LL, _D, _IP, _IP, _DP, _DP]),
+    # per-cell spot pickers
+    "ia3_cellpick_create": (_I, [_DP, _BP, _IP, _IP, _IP, _DP, _IP, _IP, _I, _I, _DP, _H]),
+    "ia3_cellpick_free": (None, [_H]),
+    "ia3_cellpick_merge_dev": (_I, [_H, _I, _D, _I, _D, _IP, _IP, _IP]),
+    "ia3_cellpick_naive_dev": (_I, [_H, _I, _IP, _IP]),
+    "ia3_cellpick_plan": (_I, [_H, _IP, _IP, _LP]),
+    "ia3_cellpick_forward_dev": (_I, [_H, _IP, _I, _DP, _I, _DP, _IP, _DP, _DP, _D, _D, _D, _I, _DP, _BP, _IP]),
     # whole round-folder movies
     "ia3_process_movies": (_I, [_MOVJ, _I, _MOVP]),
 }
@@ -1985,3 +1995,217 @@ class ScorePopulation(Owner):
 
     def _release(self, handle):
         lib().ia3_score_free(handle)
+
+
+# ---- per-cell spot pickers (csrc/cellpick.hip) ----------------------------------------------------------------------------------
+def cellpick_cdf_table(ref, weight, limit_lo, limit_hi):
+    """(sorted reference values, table) of one chromosome's 'cdf' neighbour reference: ``table[k]`` is distance_score of a
+    distance with k reference values ``<=`` it, ``np.log(1 - _cum_prob) * weight`` (-inf where nothing is left), in the
+    arithmetic of csrc/ia3_score.h sc_cum_prob with this host's ``np.log``."""
+    s = np.sort(np.asarray(ref, dtype=np.float64).reshape(-1))
+    n = len(s)
+    with np.errstate(all="ignore"):
+        p = np.arange(n + 1) / np.float64(n)
+        min_p = np.float64(np.searchsorted(s, limit_lo, side='right')) / np.float64(n)
+        max_p = np.float64(np.searchsorted(s, limit_hi, side='right')) / np.float64(n)
+        r = p - min_p if max_p <= min_p else (p - min_p) / (max_p - min_p)
+        r[r <= 0.] = 0.
+        r[np.isnan(r)] = 1. / np.float64(n)
+        r[r >= 1.] = 1.
+        cdf = 1 - r
+        table = np.full(n + 1, -np.inf)
+        table[cdf > 0] = np.log(cdf[cdf > 0]) * float(weight)
+    return s, table
+
+
+class CellPickPopulation(Owner):
+    """The candidate spots of many cells resident in HBM (owner of an ``ia3_cellpick_create`` handle): CSR over cell x region
+    x chromosome of (h, z, x, y) rows in pixels, the cells' region ids and chromosome coordinates and the pixel sizes.
+    ``merge`` makes the merged lists on the device, where they stay; ``forward`` takes per-spot scores up and brings
+    dynamic scores and pointers back.  The host keeps the callers' full-width rows, from which results are put together."""
+
+    def __init__(self, handle):
+        self._h = handle
+        self.merged = False
+
+    @classmethod
+    def upload(cls, cells, distance_zxy):
+        """``cells``: a list of ``(cell_cand_spots, region_ids, chrom_coords)``; ``cell_cand_spots[region][chromosome]`` is a
+        table of spots (intensity, z, x, y, ...) or empty, ``chrom_coords`` a list of (z, x, y) in pixels or None.
+        NotImplementedError for more than IA3_CELLPICK_MAX_CHROM chromosomes in a cell."""
+        MC = IA3_CELLPICK_MAX_CHROM
+        if len(cells) < 1:
+            raise ValueError("cell pickers: no cell")
+        dz = np.ascontiguousarray(distance_zxy, dtype=np.float64).reshape(-1)
+        if len(dz) != 3:
+            raise ValueError("cell pickers: distance_zxy of %d values" % len(dz))
+        self = cls(None)
+        self.n_cells = len(cells)
+        self.n_chrom = np.zeros(self.n_cells, dtype=np.int32)
+        self.has_coords = np.zeros(self.n_cells, dtype=np.int32)
+        self.coords = np.zeros((self.n_cells, MC, 3))
+        self.region_ids, self.width, self.cell_rows = [], [], []
+        counts, parts, region_start = [], [], [0]
+        for k, (cand, ids, coords) in enumerate(cells):
+            C_k = len(coords) if coords is not None else len(cand[0])
+            if C_k > MC:
+                raise NotImplementedError("cell pickers: %d chromosomes in cell %d (at most %d are built: a spot of the next region "
+                                          "walks up to C^C index tuples)" % (C_k, k, MC))
+            if C_k < 1 or len(cand) < 1:
+                raise ValueError("cell pickers: cell %d has no chromosome or no region" % k)
+            if len(ids) != len(cand):
+                raise ValueError("cell pickers: cell %d has %d regions and %d region ids" % (k, len(cand), len(ids)))
+            self.n_chrom[k] = C_k
+            if coords is not None:
+                self.has_coords[k] = 1
+                self.coords[k, :C_k] = np.array([np.asarray(c, dtype=np.float64).reshape(3) for c in coords])
+            ids = np.array(ids)
+            if ids.dtype.kind == 'f' and not np.isfinite(ids).all():
+                raise ValueError("cell pickers: a region id of cell %d is not a number" % k)
+            ids = ids.astype(np.int64)
+            if len(ids) and (ids.min() < -2**31 or ids.max() > 2**31 - 1):
+                raise ValueError("cell pickers: a region id of cell %d lies outside int32" % k)
+            self.region_ids.append(ids)
+            width, rows_k = None, []
+            for r, lists in enumerate(cand):
+                if len(lists) != C_k:
+                    raise NotImplementedError("cell pickers: region %d of cell %d has %d spot lists for %d chromosomes" % (r, k, len(lists), C_k))
+                for c in range(MC):
+                    if c >= C_k or len(lists[c]) == 0:
+                        counts.append(0)
+                        continue
+                    t = np.array(lists[c], dtype=np.float64)
+                    if t.ndim != 2 or t.shape[1] < 4:
+                        raise IndexError("cell pickers: the spots of region %d, chromosome %d of cell %d have shape %s" % (r, c, k, t.shape))
+                    if width is None:
+                        width = t.shape[1]
+                    elif width != t.shape[1]:
+                        raise ValueError(f"_spot object length is not unique, exit")
+                    rows_k.append(t)
+                    counts.append(len(t))
+            self.width.append(11 if width is None else width)
+            self.cell_rows.append(np.concatenate(rows_k) if rows_k else np.zeros((0, self.width[-1])))
+            parts.append(self.cell_rows[-1][:, :4])
+            region_start.append(region_start[-1] + len(cand))
+        self.G = region_start[-1]
+        self.region_start = np.array(region_start, dtype=np.int32)
+        total = np.concatenate([[0], np.cumsum(np.array(counts, dtype=np.int64))])
+        if total[-1] > 2**31 - 1 or self.G * MC + 1 > 2**31 - 1:
+            raise NotImplementedError("cell pickers: %d candidate rows in one population" % total[-1])
+        self.cand_start = total.astype(np.int32)
+        self.cell_cand0 = self.cand_start[self.region_start * MC]
+        self.rows = np.ascontiguousarray(np.concatenate(parts)) if total[-1] else np.zeros((0, 4))
+        self.row_nan = np.ascontiguousarray(np.concatenate([np.isnan(t).any(axis=1) for t in self.cell_rows]).astype(np.uint8))
+        self.region_cell = np.repeat(np.arange(self.n_cells), np.diff(self.region_start))
+        per_region = self.cand_start[MC::MC] - self.cand_start[:-1:MC]
+        cap = np.concatenate([[0], np.cumsum(per_region.astype(np.int64) + 2 * self.n_chrom[self.region_cell])])
+        if cap[-1] * MC > 2**31 - 1:   # the planes of a forward pass, at their most
+            raise NotImplementedError("cell pickers: room for %d merged rows in one population" % cap[-1])
+        self.cap_start = cap.astype(np.int32)
+        self.cap = int(cap[-1])
+        self.planes = int(self.n_chrom.max())             # score / pointer planes of a forward pass
+        self.dzxy = dz
+        h = C.c_void_p()
+        rows = self.rows.reshape(-1) if self.rows.size else np.zeros(1)
+        nan = self.row_nan if self.row_nan.size else np.zeros(1, dtype=np.uint8)
+        check(lib().ia3_cellpick_create(ptr(rows), ptr(nan), ptr(self.cand_start), ptr(self.region_start), ptr(self.n_chrom),
+                                        ptr(self.coords.reshape(-1)), ptr(self.has_coords), ptr(self.cap_start), self.n_cells, self.G, ptr(dz), C.byref(h)))
+        self._h = h
+        return self
+
+    def merge(self, intensity_th=0., hard_intensity_th=True, dist_th=0.1):
+        """``ia3_cellpick_merge_dev``: merge_spot_list of every region; sets ``mcount`` / ``mvalid`` (G) and ``msrc``."""
+        self.mcount = np.zeros(self.G, dtype=np.int32)
+        self.mvalid = np.zeros(self.G, dtype=np.int32)
+        self.msrc = np.zeros(max(self.cap, 1), dtype=np.int32)
+        check(lib().ia3_cellpick_merge_dev(self._h, 0 if intensity_th is None else 1, 0. if intensity_th is None else float(intensity_th),
+                                           1 if hard_intensity_th else 0, float(dist_th), ptr(self.mcount), ptr(self.mvalid), ptr(self.msrc)))
+        self.merged = True
+        # the places of the merged rows among the room the regions were given, region after region
+        region = np.repeat(np.arange(self.G), np.diff(self.cap_start))
+        self.mpos = np.where(np.arange(self.cap) - self.cap_start[region] < self.mcount[region])[0]
+        self.mregion = region[self.mpos]
+        self.mstart = np.concatenate([[0], np.cumsum(self.mcount)])     # offsets into mpos per region
+
+    def merged_rows4(self):
+        """(M, 4) rows (h, z, x, y) of all merged spots, region after region: what the device keeps."""
+        src = self.msrc[self.mpos]
+        out = np.zeros((len(src), 4))
+        real = src >= 0
+        out[real] = self.rows[src[real]]
+        out[~real, 1:4] = self.coords[self.region_cell[self.mregion[~real]], -(src[~real] + 1)]
+        return out
+
+    def merged_region(self, g):
+        """The merged spots of region g as the reference returns them: (K, width) rows, ``np.array([])`` for none."""
+        k = self.region_cell[g]
+        src = self.msrc[self.cap_start[g]:self.cap_start[g] + self.mcount[g]]
+        if len(src) == 0:
+            return np.array([])
+        MC = IA3_CELLPICK_MAX_CHROM
+        width = self.width[k] if self.cand_start[(g + 1) * MC] > self.cand_start[g * MC] else 11
+        out = np.full((len(src), width), np.nan)
+        for i, s in enumerate(src):
+            if s >= 0:
+                out[i] = self.cell_rows[k][s - self.cell_cand0[k]]
+            else:
+                out[i, 0] = 0
+                out[i, 1:4] = self.coords[k, -(s + 1)]
+        return out
+
+    def naive(self, mode):
+        """``ia3_cellpick_naive_dev``: (pick, sub), each (G, IA3_CELLPICK_MAX_CHROM)."""
+        pick = np.zeros((self.G, IA3_CELLPICK_MAX_CHROM), dtype=np.int32)
+        sub = np.zeros((self.G, IA3_CELLPICK_MAX_CHROM), dtype=np.int32)
+        check(lib().ia3_cellpick_naive_dev(self._h, int(mode), ptr(pick.reshape(-1)), ptr(sub.reshape(-1))))
+        return pick, sub
+
+    def plan(self, vstart, vreg, vgap):
+        vstart = np.ascontiguousarray(vstart, dtype=np.int32)
+        vreg = np.ascontiguousarray(vreg if len(vreg) else [0], dtype=np.int32)
+        vgap = np.ascontiguousarray(vgap if len(vgap) else [0], dtype=np.int64)
+        check(lib().ia3_cellpick_plan(self._h, ptr(vstart), ptr(vreg), ptr(vgap)))
+
+    def forward(self, cells, scores, score_metric, refs, weight, limit_hi, nan_mask, share):
+        """``ia3_cellpick_forward_dev``.  ``scores``: (planes, cap), one plane per chromosome up to the largest number of
+        chromosomes a cell of the population has; ``refs[(cell, chromosome)]``: the
+        reference distance ('linear') or the (sorted values, table) of ``cellpick_cdf_table`` ('cdf').
+        Returns (dy, ptr, err): the dynamic scores, the pointers (255: none) and the error code of every cell."""
+        MC = IA3_CELLPICK_MAX_CHROM
+        cells = np.ascontiguousarray(cells, dtype=np.int32)
+        scores = np.ascontiguousarray(scores, dtype=np.float64)
+        if scores.shape != (self.planes, self.cap):
+            raise ValueError("cell pickers: scores of shape %s" % (scores.shape,))
+        J = self.n_cells * MC
+        scal, rstart, srt, tab = None, None, None, None
+        if score_metric == 'linear':
+            kind = IA3_SCORE_KIND_DIST_LINEAR
+            scal = np.ones(J)
+            for (k, c), v in refs.items():
+                scal[k * MC + c] = v
+        else:
+            kind = IA3_SCORE_KIND_DIST_CDF
+            n = np.zeros(J, dtype=np.int64)
+            for (k, c), (s, t) in refs.items():
+                n[k * MC + c] = len(s)
+            rs = np.concatenate([[0], np.cumsum(n)])
+            if rs[-1] + J > 2**31 - 1:
+                raise NotImplementedError("cell pickers: %d reference values in one call" % rs[-1])
+            rstart = rs.astype(np.int32)
+            srt, tab = np.zeros(max(int(rs[-1]), 1)), np.zeros(int(rs[-1]) + J + 1)
+            for (k, c), (s, t) in refs.items():
+                j = k * MC + c
+                srt[rs[j]:rs[j + 1]] = s
+                tab[rs[j] + j:rs[j + 1] + j + 1] = t
+        dy = np.empty((self.planes, self.cap))
+        pt = np.empty((self.planes, self.cap), dtype=np.uint8)
+        err = np.zeros(self.n_cells, dtype=np.int32)
+        check(lib().ia3_cellpick_forward_dev(self._h, ptr(cells), len(cells), ptr(scores.reshape(-1)) if scores.size else ptr(np.zeros(1)), kind,
+                                             None if scal is None else ptr(scal), None if rstart is None else ptr(rstart),
+                                             None if srt is None else ptr(srt), None if tab is None else ptr(tab), float(weight), float(limit_hi),
+                                             float(nan_mask), 1 if share else 0, ptr(dy.reshape(-1)) if dy.size else ptr(np.zeros(1)),
+                                             ptr(pt.reshape(-1)) if pt.size else ptr(np.zeros(1, dtype=np.uint8)), ptr(err)))
+        return dy, pt, err
+
+    def _release(self, handle):
+        lib().ia3_cellpick_free(handle)

@@ -8,12 +8,36 @@ reference's bit for bit on the same host: distances in NumPy's two norm forms, `
 ``cum_val`` search, ``np.argmax`` / ``np.nanmax`` selection, and scores from this host's ``np.log`` (tabled per search
 node).  ``em_pick_spots`` is the loop the reference's users write around these; it is not a reference name.
 
-The per-cell pickers (``naive_pick_spots*``, ``dynamic_pick_spots*``, ``EM_pick_spots*``), ``merge_spot_list`` and
-``screen_RNA_based_on_refs`` stay the reference's.
+The per-cell pickers (csrc/cellpick.hip): ``merge_spot_list`` (:662), ``naive_pick_spots`` (:14),
+``naive_pick_spots_for_chromosomes`` (:797), ``dynamic_pick_spots_for_chromosomes`` (:902) and
+``EM_pick_spots_for_chromosomes`` (:1204) with the reference's arguments, returns, messages and quirks, each the one-cell
+case of a flat form on a resident population of cells (``_lib.CellPickPopulation``; not reference names):
+``population_merge_spot_lists``, ``population_naive_pick_spots``, ``population_dynamic_pick_spots`` and
+``population_EM_pick_spots`` take a list of cells ``(cell_cand_spots, region_ids, chrom_coords)`` and return per cell what
+the reference's function returns for it.  The candidates go up once, the merged lists are made and kept on the device, the
+forward pass of the dynamic program runs one workgroup per cell, and per EM iteration per-spot scores go up and dynamic
+scores and pointers come back; the E-step's references and scores come from a ``_lib.ScorePopulation`` of every
+(cell, chromosome), ``np.log`` is this host's.  The backward pass and the reference's bookkeeping are host Python.
+``_optimized_score_combinations`` and ``_all_score_combinations`` (:1531, :1552) are host functions.
+
+THE TIE RULE.  The reference sorts with ``np.argsort``'s default kind, which is not stable: on equal keys its order, and
+with it the reference's own output, depends on the host's CPU.  Here equal keys are taken by ascending index, NaN last
+(``kind='stable'``); the fixture is the reference run with its argsort pinned to that order.
+
+LIMITS, each NotImplementedError: at most ``_lib.IA3_CELLPICK_MAX_CHROM`` (6) chromosomes per cell, refused before anything
+is uploaded, and ``_lib.IA3_CELLPICK_MAX_SPOTS`` (64) merged spots per region, which only the merge can count: the merge
+kernel runs first, and the refusal comes after it and before the E-step and the forward pass.  A spot of the next region
+walks at most ``_lib.IA3_CELLPICK_MAX_TUPLES`` index tuples (more arise only when every score of a chromosome is infinite);
+beyond that the forward pass leaves the spot and the call raises.  Also not built: ``make_plot=True``, a ``dist_norm`` other
+than 2, a 'cdf' ``score_metric`` with other than 'cdf' references (and the reverse), and the legacy single-chromosome
+``dynamic_pick_spots`` (:306), ``EM_pick_spots`` (:389), ``old_spot_score_in_chromosome``, ``distance_score_in_chromosome``,
+``generate_distance_score_pool``, ``generate_spot_score_pool`` and
+``screen_RNA_based_on_refs``.
 
 All ``file:line`` citations are relative to the reference tree.
 """
 import bisect
+import itertools
 import time
 
 import numpy as np
@@ -592,3 +616,742 @@ def em_pick_spots(population_or_lists, n_iter_max=10, stop_ratio=0.99, cand_ids=
     finally:
         if own:
             pop.free()
+
+
+# ---- the per-cell pickers (:14-64, :662-765, :797-1563) ------------------------------------------------------------------------
+
+def _bad_spot(width):
+    _b = np.ones(width) * np.nan
+    _b[0] = 0
+    return _b
+
+
+def _upload_cells(cells, distance_zxy):
+    """A ``CellPickPopulation`` of ``cells`` with its per-cell host state; the caller's lists are not copied."""
+    pop = L.CellPickPopulation.upload([(_c[0], _c[1], _c[2]) for _c in cells], (1, 1, 1) if distance_zxy is None else distance_zxy)
+    pop.cells = cells
+    return pop
+
+
+def _merge(pop, intensity_th, hard_intensity_th, dist_th=0.1):
+    pop.merge(intensity_th, hard_intensity_th, dist_th)
+    pop._merged_cache = {}
+    pop._naive_cache = {}
+    pop._planned = False
+    pop._spop = None
+
+
+def _cell_merged(pop, k):
+    """merge_spot_list of every region of cell k, in the caller's region order."""
+    if k not in pop._merged_cache:
+        pop._merged_cache[k] = [pop.merged_region(_g) for _g in range(pop.region_start[k], pop.region_start[k + 1])]
+    return pop._merged_cache[k]
+
+
+def population_merge_spot_lists(cells, dist_th=0.1, dist_norm=2, intensity_th=0., hard_intensity_th=True):
+    """NOT a reference name.  ``[merge_spot_list(spot_list, ..., append_nan_spots=chrom_coords is not None,
+    chrom_coords=chrom_coords) for spot_list in cell_cand_spots]`` of every cell ``(cell_cand_spots, region_ids,
+    chrom_coords)``, merged on the device in one call."""
+    if dist_norm != 2:
+        raise NotImplementedError("merge_spot_list: dist_norm %s is not built (2, the Euclidean norm, is)" % (dist_norm,))
+    with _upload_cells(cells, None) as pop:
+        _merge(pop, intensity_th, hard_intensity_th, dist_th)
+        return [_cell_merged(pop, _k) for _k in range(pop.n_cells)]
+
+
+def merge_spot_list(spot_list, dist_th=0.1, dist_norm=2,
+                    intensity_th=0., hard_intensity_th=True,
+                    append_nan_spots=False, chrom_coords=None):
+    """picking.py:662-765 — the spots of ``spot_list`` (one table per chromosome) without those within ``dist_th`` pixels of
+    an earlier kept spot and, with ``intensity_th``, without the dim ones (``hard_intensity_th=False`` keeps at least
+    ``len(spot_list)`` of the brightest); with ``append_nan_spots`` a placeholder row (0, chromosome coordinate, NaN ...)
+    stands for every chromosome that has no list and is appended for every chromosome that owns no kept spot."""
+    if append_nan_spots and chrom_coords is None:
+        raise ValueError(f"chrom_coords should be given if append_nan_spots is True")
+    if dist_norm != 2:
+        raise NotImplementedError("merge_spot_list: dist_norm %s is not built (2, the Euclidean norm, is)" % (dist_norm,))
+    if len(spot_list) == 0 or (not append_nan_spots and all(len(_s) == 0 for _s in spot_list)):
+        if append_nan_spots:
+            raise NotImplementedError("merge_spot_list: no spot list with append_nan_spots fails in the reference (:749) and is not built")
+        return np.array([])
+    return population_merge_spot_lists([([spot_list], [0], chrom_coords if append_nan_spots else None)], dist_th, dist_norm,
+                                       intensity_th, hard_intensity_th)[0][0]
+
+
+def _naive_own(lists):
+    """Per entry of ``lists`` (a table of spots or empty) the place of the brightest spot by the pinned argsort, -1 for an
+    empty entry, picked on the device."""
+    if len(lists) == 0:
+        return np.zeros(0, dtype=int)
+    with _upload_cells([([[_l] for _l in lists], np.arange(len(lists)), None)], None) as pop:
+        pick, _ = pop.naive(L.IA3_CELLPICK_NAIVE_OWN)
+        return np.where(pick[:, 0] < 0, -1, pick[:, 0] - pop.cand_start[:-1:L.IA3_CELLPICK_MAX_CHROM])
+
+
+def naive_pick_spots(cand_spots, region_ids, use_chrom_coord=True, chrom_id=None,
+                     return_indices=False, verbose=True):
+    """picking.py:14-64 — Naive pick spots simply by intensity."""
+    if len(cand_spots) != len(region_ids):
+        raise ValueError(
+            "cand_spots and region_ids should have the same length!")
+    if chrom_id is None and use_chrom_coord:
+        raise ValueError(
+            f"chrom_id should be given if use_chrom_coord is True!")
+    elif chrom_id is not None and not isinstance(chrom_id, int):
+        chrom_id = int(chrom_id)
+    _lists = []
+    for _spots, _id in zip(cand_spots, region_ids):
+        if use_chrom_coord:
+            if len(_spots) <= chrom_id:
+                raise IndexError(
+                    f" spots:{_spots} for region:{_id} doesn't have spots for chromosome {chrom_id}")
+            _lists.append(np.array(_spots[chrom_id]))
+        else:
+            _lists.append(np.array(_spots))
+    _inds = _naive_own(_lists)
+    _selected_spots = []
+    for _pts, _ind in zip(_lists, _inds):
+        if _ind < 0:
+            _bad_pt = np.nan * np.ones(11)
+            if not use_chrom_coord:
+                _bad_pt[0] = 0
+            _selected_spots.append(_bad_pt)
+        else:
+            _selected_spots.append(_pts[_ind])
+    if return_indices:
+        return np.array(_selected_spots), np.array(_inds, dtype=int)
+    else:
+        return np.array(_selected_spots)
+
+
+def _naive_cell(pop, k, chrom_share_spots, distance_zxy):
+    """naive_pick_spots_for_chromosomes (:834-892) of cell k of a merged population: (_sel_spot_list, _sel_spot_inds)."""
+    cell_cand_spots, region_ids, chrom_coords = pop.cells[k][:3]
+    _merged_spot_list = _cell_merged(pop, k)
+    _num_chroms = int(pop.n_chrom[k])
+    _spot_obj_len = [np.array(_s[0]).shape[1] for _s in cell_cand_spots if len(_s) > 0 and len(_s[0]) > 0]
+    if len(_spot_obj_len) == 0:
+        _spot_obj_len = 11
+    elif len(np.unique(_spot_obj_len)) == 1:
+        _spot_obj_len = np.unique(_spot_obj_len)[0]
+    else:
+        raise ValueError(f"_spot object length is not unique, exit")
+    _bad = _bad_spot(_spot_obj_len)
+    g0, g1 = pop.region_start[k], pop.region_start[k + 1]
+    if chrom_coords is None or chrom_share_spots:
+        if L.IA3_CELLPICK_NAIVE_OWN not in pop._naive_cache:
+            pop._naive_cache[L.IA3_CELLPICK_NAIVE_OWN] = pop.naive(L.IA3_CELLPICK_NAIVE_OWN)
+        pick = pop._naive_cache[L.IA3_CELLPICK_NAIVE_OWN][0][g0:g1]
+        _sel_spot_list = [np.array([pop.cell_rows[k][_p - pop.cell_cand0[k]] if _p >= 0 else np.nan * np.ones(11) for _p in pick[:, _i]])
+                          for _i in range(_num_chroms)]
+        _sel_spot_inds = [-1 * np.ones(len(_merged_spot_list), dtype=int) for _i in range(_num_chroms)]
+    else:
+        distance_zxy[np.newaxis, :]                   # :870 refuses a list, the package's default included
+        if L.IA3_CELLPICK_NAIVE_MERGED not in pop._naive_cache:
+            pop._naive_cache[L.IA3_CELLPICK_NAIVE_MERGED] = pop.naive(L.IA3_CELLPICK_NAIVE_MERGED)
+        pick, sub = pop._naive_cache[L.IA3_CELLPICK_NAIVE_MERGED]
+        _sel_spot_list = [[] for _i in range(_num_chroms)]
+        _sel_spot_inds = [[] for _i in range(_num_chroms)]
+        for _r, _spots in enumerate(_merged_spot_list):
+            for _chrom_id in range(_num_chroms):
+                _p = pick[g0 + _r, _chrom_id]
+                if len(_spots) == 0 or _p < 0:
+                    _sel_spot_list[_chrom_id].append(_bad.copy())
+                    _sel_spot_inds[_chrom_id].append(-1)
+                else:
+                    _sel_spot_list[_chrom_id].append(_spots[_p])
+                    _sel_spot_inds[_chrom_id].append(int(sub[g0 + _r, _chrom_id]))
+        _sel_spot_list = [np.array(_spots) for _spots in _sel_spot_list]
+        _sel_spot_inds = [np.array(_inds) for _inds in _sel_spot_inds]
+    return _sel_spot_list, _sel_spot_inds
+
+
+def _check_cells(cells):
+    """What is refused before anything is uploaded; the number of chromosomes of every cell."""
+    nums = []
+    for _cand, _ids, _coords in [_c[:3] for _c in cells]:
+        _n = len(_coords) if _coords is not None else len(_cand[0])
+        if _n > L.IA3_CELLPICK_MAX_CHROM:
+            raise NotImplementedError("%d chromosomes in a cell: at most %d are picked together (a spot of the next region walks "
+                                      "up to C^C index tuples)" % (_n, L.IA3_CELLPICK_MAX_CHROM))
+        nums.append(_n)
+    return nums
+
+
+def population_naive_pick_spots(cells, intensity_th=0., hard_intensity_th=True, chrom_share_spots=False,
+                                distance_zxy=_distance_zxy, return_indices=False, verbose=True):
+    """NOT a reference name.  ``naive_pick_spots_for_chromosomes`` of every cell ``(cell_cand_spots, region_ids,
+    chrom_coords)``: a list with, per cell, what the reference returns for it."""
+    nums = _check_cells(cells)
+    out = [None] * len(cells)
+    live = [_k for _k, _n in enumerate(nums) if _n > 0]
+    for _k, _n in enumerate(nums):
+        if _n == 0:
+            out[_k] = ([], []) if return_indices else []
+    if live:
+        with _upload_cells([cells[_k] for _k in live], (1, 1, 1) if isinstance(distance_zxy, list) else distance_zxy) as pop:
+            _merge(pop, intensity_th, hard_intensity_th)
+            for _j, _k in enumerate(live):
+                _spots, _inds = _naive_cell(pop, _j, chrom_share_spots, distance_zxy)
+                out[_k] = (_spots, _inds) if return_indices else _spots
+    return out
+
+
+def naive_pick_spots_for_chromosomes(cell_cand_spots, region_ids, chrom_coords=None,
+                                     intensity_th=0., hard_intensity_th=True,
+                                     chrom_share_spots=False, distance_zxy=_distance_zxy,
+                                     return_indices=False, verbose=True):
+    """picking.py:797-899 — per chromosome the brightest spot of every region: among its own candidates without
+    ``chrom_coords`` or with ``chrom_share_spots`` (all indices are -1 then, as in the reference), else among the merged
+    spots nearest to its coordinate (the index counts within those, :885-888)."""
+    return population_naive_pick_spots([(cell_cand_spots, region_ids, chrom_coords)], intensity_th, hard_intensity_th,
+                                       chrom_share_spots, distance_zxy, return_indices, verbose)[0]
+
+
+def _index_tuples(allowed, chrom_share_spots):
+    """The tuples (one index per chromosome) of ``itertools.product`` over the chromosomes' allowed indices, in its order;
+    unless spots are shared, only those whose indices all differ."""
+    tuples = itertools.product(*allowed)
+    if chrom_share_spots:
+        return list(tuples)
+    return [t for t in tuples if len(set(t)) == len(t)]
+
+
+def _check_score_list(_score_list):
+    if len(_score_list) == 0:
+        raise ValueError(f"_score_list is empty, exit!")
+    if len(_score_list[0]) == 0:
+        raise ValueError(f"_score_list[0] is empty, no spots, exit!")
+    return len(_score_list), len(_score_list[0])
+
+
+def _all_score_combinations(_score_list, chrom_share_spots=False):
+    """picking.py:1552-1563 — every tuple of spot indices, one per chromosome.  A host function: the device walks the
+    same tuples in ``cp_pick`` (csrc/ia3_cellpick.h)."""
+    C, K = _check_score_list(_score_list)
+    return _index_tuples([np.arange(K)] * C, chrom_share_spots)
+
+
+def _optimized_score_combinations(_score_list, chrom_share_spots=False):
+    """picking.py:1531-1550 — the tuples over each chromosome's C best-scored indices (ascending by score, equal scores by
+    ascending index: the tie rule of this module), or over all indices of a chromosome whose scores are all infinite."""
+    C, K = _check_score_list(_score_list)
+    if K < C:
+        raise IndexError(f"there should be more spots than chromosomes!")
+    allowed = [np.arange(K) if np.isinf(sc).all() else np.argsort(sc, kind='stable')[K - C:] for sc in _score_list]
+    return _index_tuples(allowed, chrom_share_spots)
+
+
+def _plan(pop):
+    """The regions each cell's forward pass walks (:1066-1085): those with a merged spot without NaN, by ascending id
+    (equal ids in the caller's order)."""
+    if (pop.mcount > L.IA3_CELLPICK_MAX_SPOTS).any():
+        raise NotImplementedError("%d merged spots in one region: at most %d are built (the spots of a region are the lanes of "
+                                  "one wavefront)" % (pop.mcount.max(), L.IA3_CELLPICK_MAX_SPOTS))
+    pop.order, pop.vpos, vstart, vreg, vgap = [], [], [0], [], []
+    for _k in range(pop.n_cells):
+        _ids = pop.region_ids[_k]
+        _order = np.argsort(_ids, kind='stable')
+        _g = pop.region_start[_k] + _order
+        _valid = np.where((pop.mcount[_g] > 0) & (pop.mvalid[_g] > 0))[0]
+        pop.order.append(_order)
+        pop.vpos.append(_valid)                         # _id_indices
+        vreg.extend(_g[_valid].tolist())
+        _vid = _ids[_order][_valid]
+        vgap.extend(([0] + np.diff(_vid).tolist()) if len(_vid) else [])
+        vstart.append(len(vreg))
+    pop.vstart = np.array(vstart)
+    pop.vreg = np.array(vreg, dtype=np.int64)
+    pop.plan(vstart, vreg, vgap)
+    pop._planned = True
+
+
+def _spot_scores(spop, score_metric, ref_metric, intensity_th, local_size, weights, distance_limits, nan_mask, inf_mask, ignore_nan):
+    """Per chromosome of a ScorePopulation what ``generate_ref_from_chromosome`` returns for its selected spots and the sum
+    ct + lc + int of ``spot_score_in_chromosome`` (:306-407) of its candidates against them."""
+    arrays, counts, scalars = spop.references(ref_metric, local_size, intensity_th, ignore_nan)
+    w = [float(weights[0]), float(weights[1]), 0., float(weights[2])]
+    val, cls, ref_counts = spop.scores(score_metric, ref_metric, local_size, intensity_th, ignore_nan, w, distance_limits)
+    if score_metric == 'cdf':
+        for a in range(2):
+            if w[a] != 0. and (ref_counts[:, a] == 0).any():
+                raise ValueError(f"Wrong input ref_dist, not enough values to calculate cdf")
+        if (ref_counts[:, 3] == 0).any():
+            raise ValueError(f"Wrong input data, no valid points at all.")
+    from .scoring import _finish, _reference_values, _say_fallbacks
+    total = None
+    for a in (0, 1, 3):
+        s = _finish(val[a], cls[a], w[a], val[a].shape)
+        if a < 3:
+            if w[a] == 0.:
+                s = np.zeros(s.shape)
+            else:
+                s[(cls[a] & L.SCORE_NAN_IN) != 0] = nan_mask
+        else:
+            s[np.isnan(s)] = nan_mask
+            s[np.isinf(s)] = inf_mask
+        total = s if total is None else total + s
+    refs = []
+    for c in range(spop.C):
+        _say_fallbacks(counts[c])
+        refs.append(_reference_values(arrays[c], counts[c], scalars[c], ref_metric, ignore_nan))
+    at = spop.cand_start
+    return refs, [total[at[c]:at[c + 1]] for c in range(spop.C)]
+
+
+def _reference_ids(cell_cand_spots, region_ids, ref_spot_list, ref_spot_ids, spot_num_th):
+    """The region id of every reference spot, per chromosome (:999-1025).  A chromosome with at least ``spot_num_th``
+    reference spots keeps them, with ``ref_spot_ids``, the region ids when there is one spot per region, or 0 .. n-1.  One
+    with fewer takes ALL its candidates as references -- written into ``ref_spot_list``, which the reference does too --
+    each with the label of its region: ``ref_spot_ids`` when it has one entry per region, the region ids when it is not
+    given, the region's position otherwise."""
+    R = len(cell_cand_spots)
+    if ref_spot_ids is None:
+        labels = region_ids
+    elif len(ref_spot_ids) == R:
+        labels = ref_spot_ids
+    else:
+        labels = np.arange(R)
+    ids = []
+    for c in range(len(ref_spot_list)):
+        n = len(ref_spot_list[c])
+        if n >= spot_num_th:
+            if ref_spot_ids is not None:
+                ids.append(np.array(ref_spot_ids, dtype=int))
+            else:
+                ids.append(region_ids if n == len(region_ids) else np.arange(n))
+            continue
+        lists = [lists_r[c] for lists_r in cell_cand_spots]
+        ref_spot_list[c] = np.concatenate(lists)
+        ids.append(np.repeat(np.asarray(labels, dtype=np.float64)[:R], [len(t) for t in lists]))
+    return ids
+
+
+def _trace_back(pop, dy, ptr, walked, c):
+    """The backward pass (:1158-1169) of chromosome c over the regions ``walked``: the first best dynamic score of the last
+    region, then the stored pointers; the picked merged-spot index of every walked region."""
+    at = pop.cap_start[walked]
+    picks = np.empty(len(walked), dtype=int)
+    picks[-1] = np.argmax(dy[c, at[-1]:at[-1] + pop.mcount[walked[-1]]])
+    for j in range(len(walked) - 1, 0, -1):
+        picks[j - 1] = ptr[c, at[j] + picks[j]]
+    return picks
+
+
+def _assemble(merged_sorted, order, walked_pos, picks, n_chrom):
+    """What the dynamic picker returns for one cell (:1171-1194), in the caller's region order: per chromosome the picked
+    spot and its index for the walked regions (a spot that holds a NaN -- a placeholder -- comes back as the bad spot but
+    keeps its index), the bad spot and -1 for the others; tables of zeros when nothing was walked."""
+    R, width = len(merged_sorted), merged_sorted[0].shape[1]
+    spots = [np.zeros((R, width)) for _c in range(n_chrom)]
+    inds = [np.full(R, -1, dtype=int) for _c in range(n_chrom)]
+    for c in range(len(picks)):
+        rows = [merged_sorted[j][i] for j, i in zip(walked_pos, picks[c])]
+        spots[c][:] = _bad_spot(len(rows[-1]))
+        for j, i, row in zip(walked_pos, picks[c], rows):
+            spots[c][order[j]] = _bad_spot(len(row)) if np.isnan(row).any() else row
+            inds[c][order[j]] = i
+    return spots, inds
+
+
+def _dynamic_cells(pop, ks, sel_lists, ref_lists, ref_spot_ids, nb_dist_list, P):
+    """dynamic_pick_spots_for_chromosomes (:958-1200) of the cells ``ks`` of a merged population, with the reference's
+    bookkeeping per cell on the host, one E-step and one forward pass for all of them.  ``sel_lists[k]`` / ``ref_lists[k]``:
+    the caller's sel_spot_list / ref_spot_list or None.  Returns {k: (_sel_spot_list, _sel_ind_list)}."""
+    MC = L.IA3_CELLPICK_MAX_CHROM
+    score_metric, ref_metric = P["score_metric"], P["ref_dist_metric"]
+    if not pop._planned:
+        _plan(pop)
+    st = {}
+    _t0 = time.time()
+    cand_t, cand_i, sel_t, sel_i, ctrs, slots = [], [], [], [], [], []
+    for k in ks:
+        cell_cand_spots, region_ids, chrom_coords = pop.cells[k][:3]
+        _merged = _cell_merged(pop, k)
+        _order = np.argsort(region_ids, kind='stable')
+        _merged_spot_list = [_merged[_id] for _id in _order]
+        _num_chroms = int(pop.n_chrom[k])
+        sel_spot_list = sel_lists.get(k)
+        if sel_spot_list is None:
+            if P["verbose"]:
+                print(f"-- initiate dynamic picking by naive picking spots.")
+            sel_spot_list, _ = _naive_cell(pop, k, P["chrom_share_spots"], P["distance_zxy"])
+            for _chrom_id in range(_num_chroms):
+                sel_spot_list[_chrom_id] = np.array([sel_spot_list[_chrom_id][_id] for _id in _order])
+        if nb_dist_list is not None:
+            raise IndexError(f"Length of nb_dist_list{len(nb_dist_list)} doesn't match length of sel_spot_list:{len(sel_spot_list)}")
+        ref_spot_list = ref_lists.get(k)
+        if ref_spot_list is None:
+            ref_spot_list = sel_spot_list             # one list, as in the reference: what follows writes into it
+        ref_id_list = _reference_ids(cell_cand_spots, region_ids, ref_spot_list, ref_spot_ids, P["spot_num_th"])
+        P["distance_zxy"][np.newaxis, :]              # scoring.py:243 refuses a list, the package's default included
+        g0, g1 = pop.region_start[k], pop.region_start[k + 1]
+        m0, m1 = pop.mstart[g0], pop.mstart[g1]
+        rows4 = pop._rows4[m0:m1]
+        ids4 = pop.region_ids[k][pop.mregion[m0:m1] - g0]
+        for _chrom_id, (_ref_spots, _ref_ids) in enumerate(zip(ref_spot_list, ref_id_list)):
+            if chrom_coords is not None and not P["update_chrom_coords"]:
+                _chrom_coord = chrom_coords[_chrom_id]
+            else:
+                _chrom_coord = None
+            if len(_ref_ids) != len(_ref_spots):
+                raise IndexError(f"chr:{_chrom_id}, Length of _ref_ids:{len(_ref_ids)} doesn't match length of _ref_spots:{len(_ref_spots)}")
+            if any(len(_s) == 0 for _s in _merged_spot_list):
+                raise IndexError("too many indices for array: array is 1-dimensional, but 2 were indexed")   # :346 on an empty region
+            if pop.vstart[k + 1] == pop.vstart[k]:
+                continue                              # no region is walked: the scores of this cell are never read
+            if len(_ref_spots) == 0:
+                raise NotImplementedError("chromosome %d has no reference spot at all, which is not built" % _chrom_id)
+            cand_t.append(rows4)
+            cand_i.append(ids4)
+            sel_t.append(np.array(_ref_spots))
+            sel_i.append(np.array(_ref_ids, dtype=int))
+            ctrs.append(_chrom_coord)
+            slots.append((k, _chrom_id))
+        st[k] = (_merged_spot_list, _order, _num_chroms)
+    # the E-step: references and scores of every (cell, chromosome) from one ScorePopulation
+    _tm = P.get("timings")
+    _t1 = time.time()
+    if _tm is not None:
+        _tm["host_before_s"] = _tm.get("host_before_s", 0.) + _t1 - _t0
+    L.score_half(P["local_size"])
+    key = tuple(slots)
+    if not slots:
+        refs, totals = [], []
+    elif pop._spop is not None and pop._spop_key == key:
+        pop._spop.replace_selected(sel_t, sel_i)
+    else:
+        if pop._spop is not None:
+            pop._spop.free()
+        pop._spop = L.ScorePopulation.upload(cand_t, cand_i, sel_t, sel_i, ctrs, P["distance_zxy"])
+        pop._spop_key = key
+    if slots:
+        refs, totals = _spot_scores(pop._spop, score_metric, ref_metric, P["intensity_th"], P["local_size"],
+                                    (P["w_ctdist"], P["w_lcdist"], P["w_int"]), P["distance_limits"], P["nan_mask"], P["inf_mask"], P["ignore_nan"])
+    scores = np.zeros((pop.planes, pop.cap))
+    nb = {}
+    w_nb = float(P["w_nbdist"])
+    for (k, c), _ref, _tot in zip(slots, refs, totals):
+        g0, g1 = pop.region_start[k], pop.region_start[k + 1]
+        scores[c, pop.mpos[pop.mstart[g0]:pop.mstart[g1]]] = _tot
+        if w_nb == 0.:
+            continue
+        if score_metric == 'linear':
+            nb[(k, c)] = float(_ref[2])
+        else:
+            from .scoring import _no_nan
+            nb[(k, c)] = L.cellpick_cdf_table(_no_nan(_ref[2], f"Wrong input ref_dist, not enough values to calculate cdf"), w_nb,
+                                              min(P["distance_limits"]), max(P["distance_limits"]))
+    if score_metric == 'cdf' and w_nb == 0.:
+        for _slot in slots:
+            nb[_slot] = (np.zeros(1), np.zeros(2))
+    # the forward pass (:1093-1155)
+    _t2 = time.time()
+    if _tm is not None:
+        _tm["e_step_s"] = _tm.get("e_step_s", 0.) + _t2 - _t1
+    walk = [k for k in ks if pop.vstart[k + 1] - pop.vstart[k] > 0]
+    for k in walk:
+        _v = pop.vreg[pop.vstart[k]:pop.vstart[k + 1]]
+        if not P["chrom_share_spots"] and (pop.mcount[_v[:-1]] < pop.n_chrom[k]).any():
+            raise ValueError(f"Not enough _inds combinations")
+    if walk:
+        dy, ptr, err = pop.forward(sorted(walk), scores, score_metric, nb, w_nb, max(P["distance_limits"]), P["nan_mask"],
+                                   P["chrom_share_spots"])
+        if (err == 1).any():
+            raise ValueError(f"Not enough _inds combinations")
+        if (err == 2).any():
+            raise ValueError("attempt to get argmax of an empty sequence")
+        if (err == 3).any():
+            raise NotImplementedError("more than %d index tuples for one spot: every score of a chromosome is infinite, so all its "
+                                      "spots are allowed, which is not walked" % L.IA3_CELLPICK_MAX_TUPLES)
+    _t3 = time.time()
+    if _tm is not None:
+        _tm["forward_s"] = _tm.get("forward_s", 0.) + _t3 - _t2
+    out = {}
+    for k in ks:
+        _merged_spot_list, _order, _num_chroms = st[k]
+        _v = pop.vreg[pop.vstart[k]:pop.vstart[k + 1]]
+        picks = [_trace_back(pop, dy, ptr, _v, _c) for _c in range(_num_chroms)] if len(_v) else []
+        _sel_spot_list, _sel_ind_list = _assemble(_merged_spot_list, _order, pop.vpos[k], picks, _num_chroms)
+        out[k] = (_sel_spot_list, _sel_ind_list)
+    if _tm is not None:
+        _tm["host_after_s"] = _tm.get("host_after_s", 0.) + time.time() - _t3
+    return out
+
+
+def _dynamic_params(ref_dist_metric, spot_num_th, intensity_th, score_metric, local_size, w_ctdist, w_lcdist, w_int, w_nbdist,
+                    ignore_nan, nan_mask, inf_mask, update_chrom_coords, chrom_share_spots, distance_zxy, distance_limits, verbose):
+    score_metric, ref_dist_metric = str(score_metric), str(ref_dist_metric)
+    if (score_metric == 'cdf') != (ref_dist_metric.lower() == 'cdf') and score_metric in ('linear', 'cdf'):
+        raise NotImplementedError("score_metric %r with ref_dist_metric %r is not built: 'cdf' scores take 'cdf' references and "
+                                  "'linear' scores one number" % (score_metric, ref_dist_metric))
+    return dict(ref_dist_metric=ref_dist_metric.lower(), spot_num_th=spot_num_th, intensity_th=intensity_th, score_metric=score_metric,
+                local_size=local_size, w_ctdist=w_ctdist, w_lcdist=w_lcdist, w_int=w_int, w_nbdist=w_nbdist, ignore_nan=ignore_nan,
+                nan_mask=nan_mask, inf_mask=inf_mask, update_chrom_coords=update_chrom_coords, chrom_share_spots=chrom_share_spots,
+                distance_zxy=distance_zxy, distance_limits=distance_limits, verbose=verbose)
+
+
+def _open_cells(pop_cells, distance_zxy, intensity_th, hard_intensity_th):
+    pop = _upload_cells(pop_cells, (1, 1, 1) if isinstance(distance_zxy, list) else distance_zxy)
+    try:
+        _merge(pop, intensity_th, hard_intensity_th)
+        pop._rows4 = pop.merged_rows4()
+    except Exception:
+        pop.free()
+        raise
+    return pop
+
+
+def _close_cells(pop):
+    if getattr(pop, "_spop", None) is not None:
+        pop._spop.free()
+    pop.free()
+
+
+def population_dynamic_pick_spots(cells, ref_spot_ids=None, ref_dist_metric='median', nb_dist_list=None, spot_num_th=100,
+                                  intensity_th=0., hard_intensity_th=True, ignore_region_ids=False, score_metric='linear',
+                                  local_size=5, w_ctdist=2, w_lcdist=1, w_int=1, w_nbdist=2,
+                                  ignore_nan=True, nan_mask=0., inf_mask=-1000.,
+                                  update_chrom_coords=False, chrom_share_spots=False,
+                                  distance_zxy=_distance_zxy, distance_limits=[200, 3000],
+                                  return_indices=False, verbose=True):
+    """NOT a reference name.  ``dynamic_pick_spots_for_chromosomes`` of every cell in one E-step and one forward pass.
+    A cell is ``(cell_cand_spots, region_ids, chrom_coords)`` and may go on with ``sel_spot_list`` and ``ref_spot_list``
+    (each a list per chromosome, or None).  Returns a list with, per cell, what the reference returns for it."""
+    nums = _check_cells(cells)
+    P = _dynamic_params(ref_dist_metric, spot_num_th, intensity_th, score_metric, local_size, w_ctdist, w_lcdist, w_int, w_nbdist,
+                        ignore_nan, nan_mask, inf_mask, update_chrom_coords, chrom_share_spots, distance_zxy, distance_limits, verbose)
+    out = [None] * len(cells)
+    live = [_k for _k, _n in enumerate(nums) if _n > 0]
+    for _k, _n in enumerate(nums):
+        if _n == 0:
+            out[_k] = ([], []) if return_indices else []
+    if live:
+        pop = _open_cells([cells[_k] for _k in live], distance_zxy, intensity_th, hard_intensity_th)
+        try:
+            sel = {_j: (cells[_k][3] if len(cells[_k]) > 3 else None) for _j, _k in enumerate(live)}
+            ref = {_j: (cells[_k][4] if len(cells[_k]) > 4 else None) for _j, _k in enumerate(live)}
+            got = _dynamic_cells(pop, list(range(len(live))), sel, ref, ref_spot_ids, nb_dist_list, P)
+        finally:
+            _close_cells(pop)
+        for _j, _k in enumerate(live):
+            out[_k] = got[_j] if return_indices else got[_j][0]
+    return out
+
+
+def dynamic_pick_spots_for_chromosomes(cell_cand_spots, region_ids,
+                                       chrom_coords=None, sel_spot_list=None,
+                                       ref_spot_list=None, ref_spot_ids=None,
+                                       ref_dist_metric='median', nb_dist_list=None, spot_num_th=100,
+                                       intensity_th=0., hard_intensity_th=True,
+                                       ignore_region_ids=False, score_metric='linear',
+                                       local_size=5, w_ctdist=2, w_lcdist=1, w_int=1, w_nbdist=2,
+                                       ignore_nan=True, nan_mask=0., inf_mask=-1000.,
+                                       update_chrom_coords=False, chrom_share_spots=False,
+                                       distance_zxy=_distance_zxy, distance_limits=[200,3000],
+                                       return_indices=False, verbose=True):
+    """picking.py:902-1200 — pick one spot per region and chromosome by dynamic programming over the regions in id order:
+    the spot scores (E-step, against references made from ``sel_spot_list``, by default the naive picks) plus the
+    neighbour-distance scores between consecutive regions, all chromosomes of the cell optimised together.
+    Outputs: _sel_spot_list, and with ``return_indices`` _sel_ind_list (indices into the merged spots of each region)."""
+    return population_dynamic_pick_spots([(cell_cand_spots, region_ids, chrom_coords, sel_spot_list, ref_spot_list)], ref_spot_ids,
+                                         ref_dist_metric, nb_dist_list, spot_num_th, intensity_th, hard_intensity_th, ignore_region_ids,
+                                         score_metric, local_size, w_ctdist, w_lcdist, w_int, w_nbdist, ignore_nan, nan_mask, inf_mask,
+                                         update_chrom_coords, chrom_share_spots, distance_zxy, distance_limits, return_indices, verbose)[0]
+
+
+def _drop_dim_candidates(cell_cand_spots, intensity_th):
+    """The EM's first filter (:1284-1287), which writes into the caller's lists: every non-empty table keeps its spots
+    of intensity >= min(intensity_th, its brightest).  Returns the position of the last region (None without regions):
+    the value the reference's loop variable is left with."""
+    last = None
+    for last, lists in enumerate(cell_cand_spots):
+        for c, spots in enumerate(lists):
+            if len(spots) > 0:
+                h = np.array(spots)[:, 0]
+                lists[c] = spots[h >= min(intensity_th, max(h))]
+    return last
+
+
+def _changed_share(new_ind_list, old_ind_list):
+    """The share of picked indices that differ from the previous iteration's (:1402-1411); all of a chromosome's count
+    as changed when it had none before."""
+    changed = total = 0
+    for new, old in zip(new_ind_list, old_ind_list):
+        if len(old) == 0:
+            changed += len(new)
+        else:
+            changed += int(np.count_nonzero(np.array(new, dtype=int) - np.array(old, dtype=int)))
+        total += len(new)
+    return changed / total
+
+
+def population_EM_pick_spots(cells, ref_spot_ids=None, ref_dist_metric='median', nb_dist_list=None, spot_num_th=100,
+                             num_iters=10, terminate_th=0.0025, intensity_th=0., hard_intensity_th=True, score_metric='linear',
+                             local_size=5, w_ctdist=2, w_lcdist=1, w_int=1, w_nbdist=2,
+                             distance_limits=[0, 3000], ignore_nan=True, nan_mask=0., inf_mask=-1000., update_chrom_coords=False,
+                             chrom_share_spots=False, distance_zxy=_distance_zxy,
+                             check_spots=True, check_th=-2., check_percentile=10., hard_dist_th=8000,
+                             make_plot=False, return_indices=False, return_sel_scores=False, return_other_scores=False,
+                             verbose=True, timings=None):
+    """NOT a reference name.  ``EM_pick_spots_for_chromosomes`` of every cell: the candidates go up once, the merged lists
+    stay on the device, and every iteration runs the cells that have not yet converged in one E-step and one forward pass.
+    A cell is ``(cell_cand_spots, region_ids, chrom_coords)`` and may go on with ``sel_spot_list`` and ``ref_spot_list``.
+    Returns a list with, per cell, what the reference returns for it.  ``timings``: a dict that receives the seconds of
+    the upload and merge, of every iteration (and, summed over them, of the host's bookkeeping before and after, the E-step
+    and the forward pass) and of the final check."""
+    from . import checking
+    if make_plot:
+        raise NotImplementedError("make_plot=True is not built: this package draws nothing")
+    cells = [list(_c) + [None] * (5 - len(_c)) for _c in cells]
+    for _c in cells:
+        _c[1] = np.array(_c[1], dtype=int)
+        if len(_c[0]) != len(_c[1]):
+            raise ValueError(f"Length of cell_cand_spots should match region_ids, while {len(_c[0])} and {len(_c[1])} received!")
+    if verbose:
+        print(f"-- filtering spots by intensity threshold={intensity_th}.")
+    _last_i = [_drop_dim_candidates(_c[0], intensity_th) for _c in cells]
+    nums = []
+    for _cand, _ids, _coords in [_c[:3] for _c in cells]:
+        nums.append(len(_coords) if _coords is not None else len(_cand[0]))
+    for _n, _c in zip(nums, cells):
+        if _n > 6 and num_iters > 0 and 1 >= terminate_th:
+            # :1362-1378 hands ONE chromosome's coordinate and all the chromosomes' lists to the dynamic picker
+            if _c[2] is None:
+                raise TypeError("'NoneType' object is not subscriptable")
+            if any(len(_s) == 0 for _spot_list in _c[0] for _s in _spot_list[1:]):
+                raise IndexError("list index out of range")
+            raise NotImplementedError("%d chromosomes in a cell: the reference optimises each by itself with all the chromosomes' "
+                                      "candidates (:1362-1378), which is not built" % _n)
+    _check_cells(cells)
+    P = _dynamic_params(ref_dist_metric, spot_num_th, intensity_th, score_metric, local_size, w_ctdist, w_lcdist, w_int, w_nbdist,
+                        ignore_nan, nan_mask, inf_mask, update_chrom_coords, chrom_share_spots, distance_zxy, distance_limits, verbose)
+    n_out = 1 + bool(return_indices) + bool(return_sel_scores) + bool(return_other_scores)
+    out = [None] * len(cells)
+    live = [_k for _k, _n in enumerate(nums) if _n > 0]
+    for _k, _n in enumerate(nums):
+        if _n == 0:
+            if verbose:
+                print("-- exit for no-chromosome case.")
+            out[_k] = [] if n_out == 1 else tuple([] for _a in range(n_out))
+    if not live:
+        return out
+    _t0 = time.time()
+    pop = _open_cells([cells[_k] for _k in live], distance_zxy, intensity_th, hard_intensity_th)
+    if timings is not None:
+        timings["upload_merge_s"] = time.time() - _t0
+        timings["iterations_s"] = []
+        P["timings"] = timings
+    try:
+        S = {}
+        for _j, _k in enumerate(live):
+            s = dict(sel_spot_list=cells[_k][3], ref_spot_list=cells[_k][4], check_with=_last_i[_k], iter=0, ratio=1, ratios=[], done=False)
+            if s["sel_spot_list"] is None:
+                if verbose:
+                    print(f"-- initialize EM by naively picking spots!")
+                s["sel_spot_list"], s["sel_ind_list"] = _naive_cell(pop, _j, chrom_share_spots, distance_zxy)
+            else:
+                s["sel_ind_list"] = [[] for _chrom_id in range(nums[_k])]
+            S[_j] = s
+        if num_iters == np.inf and terminate_th < 0:
+            raise ValueError(f"At least one valid termination flag required!")
+        local_size = int(local_size)
+        P["local_size"] = local_size
+        while True:
+            ks = [_j for _j, s in S.items() if not s["done"] and s["iter"] < num_iters and s["ratio"] >= terminate_th]
+            if not ks:
+                break
+            _t0 = time.time()
+            got = _dynamic_cells(pop, ks, {_j: S[_j]["sel_spot_list"] for _j in ks}, {_j: S[_j]["ref_spot_list"] for _j in ks},
+                                 ref_spot_ids, nb_dist_list, P)
+            _step = time.time() - _t0
+            if timings is not None:
+                timings["iterations_s"].append(_step)
+            for _j in ks:
+                s = S[_j]
+                s["sel_spot_list"], new = got[_j]
+                s["ratio"] = _changed_share(new, s["sel_ind_list"])
+                s["ratios"].append(s["ratio"])
+                if verbose:
+                    print(f"--- EM iter:{s['iter']}, time: {_step:.3f}, change_ratio={s['ratio']}")
+                s["iter"] += 1
+                s["sel_ind_list"][:len(new)] = new
+                if len(new):
+                    s["check_with"] = len(new) - 1
+                # the share of changed picks has hovered at the threshold for five iterations (:1420)
+                if len(s["ratios"]) > 5 and np.mean(s["ratios"][-5:]) <= 2 * terminate_th:
+                    if verbose:
+                        print("-- exit loop because of long oscillation around minimum.")
+                    s["done"] = True
+        _t0 = time.time()
+        check_kw = dict(distance_zxy=distance_zxy, distance_limits=distance_limits, intensity_th=intensity_th,
+                        ref_dist_metric=ref_dist_metric, score_metric=score_metric, local_size=local_size, w_ctdist=w_ctdist,
+                        w_lcdist=w_lcdist, w_int=w_int, ignore_nan=ignore_nan, check_th=check_th, check_percentile=check_percentile,
+                        hard_dist_th=hard_dist_th, return_sel_scores=True, return_other_scores=True, verbose=verbose)
+        for _j, _k in enumerate(live):
+            s = S[_j]
+            res = [s["sel_spot_list"]] + ([s["sel_ind_list"]] if return_indices else [])
+            if check_spots or return_sel_scores or return_other_scores:
+                # every chromosome is checked against the indices and the coordinate of ONE chromosome, the one the
+                # reference's stale loop variable names (:1430-1432): the last one, once an iteration has run
+                at = s["check_with"]
+                coord = None if cells[_k][2] is None else cells[_k][2][at]
+                checked = [checking.check_spot_scores(_cell_merged(pop, _j), _spots, cells[_k][1], s["sel_ind_list"][at], chrom_coord=coord,
+                                                      **check_kw) for _spots in s["sel_spot_list"]]
+                if check_spots:
+                    s["sel_spot_list"][:] = [np.array(_r[0]) for _r in checked]
+                res += [[np.array(_r[1]) for _r in checked]] if return_sel_scores else []
+                res += [[np.array(_r[2]) for _r in checked]] if return_other_scores else []
+            out[_k] = res[0] if len(res) == 1 else tuple(res)
+        if timings is not None:
+            timings["check_s"] = time.time() - _t0
+    finally:
+        _close_cells(pop)
+    return out
+
+
+def EM_pick_spots_for_chromosomes(cell_cand_spots, region_ids,
+                                  chrom_coords=None, sel_spot_list=None,
+                                  ref_spot_list=None, ref_spot_ids=None,
+                                  ref_dist_metric='median', nb_dist_list=None, spot_num_th=100,
+                                  num_iters=10, terminate_th=0.0025, intensity_th=0.,
+                                  hard_intensity_th=True, score_metric='linear',
+                                  local_size=5, w_ctdist=2, w_lcdist=1, w_int=1, w_nbdist=2,
+                                  distance_limits=[0,3000], ignore_nan=True,
+                                  nan_mask=0., inf_mask=-1000., update_chrom_coords=False,
+                                  chrom_share_spots=False, distance_zxy=_distance_zxy,
+                                  check_spots=True, check_th=-2., check_percentile=10.,hard_dist_th=8000,
+                                  make_plot=False, save_plot=False, save_path=None, save_filename='',
+                                  return_indices=False, return_sel_scores=False, return_other_scores=False,
+                                  verbose=True):
+    """picking.py:1204-1528 — EM spot picking for the chromosomes of one cell: start from the naive picks (or
+    ``sel_spot_list``), iterate ``dynamic_pick_spots_for_chromosomes`` with the last picks as references until fewer than
+    ``terminate_th`` of the indices change, ``num_iters`` is reached or the change has hovered near the threshold for five
+    iterations, then check the picks (``checking.check_spot_scores``).  As in the reference the first filter writes into the
+    caller's ``cell_cand_spots`` and the final check reads the last chromosome's indices and coordinate for every
+    chromosome.  ``make_plot=True`` is NotImplementedError."""
+    if verbose:
+        print(f"- EM picking spots for {len(region_ids)} regions, use chrom_coords:{(chrom_coords is not None)}")
+    return population_EM_pick_spots([[cell_cand_spots, region_ids, chrom_coords, sel_spot_list, ref_spot_list]], ref_spot_ids,
+                                    ref_dist_metric, nb_dist_list, spot_num_th, num_iters, terminate_th, intensity_th, hard_intensity_th,
+                                    score_metric, local_size, w_ctdist, w_lcdist, w_int, w_nbdist, distance_limits, ignore_nan, nan_mask,
+                                    inf_mask, update_chrom_coords, chrom_share_spots, distance_zxy, check_spots, check_th, check_percentile,
+                                    hard_dist_th, make_plot, return_indices, return_sel_scores, return_other_scores, verbose)[0]
+
+
+def _not_built(name, why):
+    def f(*args, **kwargs):
+        raise NotImplementedError("%s is not built: %s" % (name, why))
+    f.__name__ = name
+    f.__doc__ = "Not built: %s." % why
+    return f
+
+
+_LEGACY = "the single-chromosome picker is superseded by the *_for_chromosomes functions, which take one chromosome too"
+dynamic_pick_spots = _not_built("dynamic_pick_spots", _LEGACY)
+EM_pick_spots = _not_built("EM_pick_spots", _LEGACY)
+old_spot_score_in_chromosome = _not_built("old_spot_score_in_chromosome", "spot_tools.scoring.spot_score_in_chromosome replaces it")
+distance_score_in_chromosome = _not_built("distance_score_in_chromosome", "spot_tools.scoring.distance_score replaces it")
+generate_distance_score_pool = _not_built("generate_distance_score_pool", "it serves the legacy single-chromosome picker only")
+generate_spot_score_pool = _not_built("generate_spot_score_pool", "it serves the legacy single-chromosome picker only")
+screen_RNA_based_on_refs = _not_built("screen_RNA_based_on_refs", "it works on the reference's RNA data sets, which this package does not carry")

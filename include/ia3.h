@@ -983,6 +983,55 @@ int ia3_score_values_dev(const double* ref_array, int n_ref, double ref_scalar, 
 int ia3_score_neighbor_lists_dev(void* population, long long step, double invalid, const int* off_fwd, const int* off_rev,
                                  double* fwd, double* rev);
 
+/* ---- per-cell spot pickers: spot_tools/picking.py :662-1563 (csrc/cellpick.hip) ------------------
+ * ia3_cellpick_create uploads the candidates of n_cells cells once, as CSR over cell x region x chromosome: cell k owns
+ * the regions [region_start[k], region_start[k + 1]) of G in all, has n_chrom[k] chromosomes (at most
+ * IA3_CELLPICK_MAX_CHROM) and, where has_coords[k] is non-zero, their coordinates coords[(k * IA3_CELLPICK_MAX_CHROM + c)
+ * * 3 ..] in pixels; chromosome c of region g owns the rows [cand_start[g * IA3_CELLPICK_MAX_CHROM + c], cand_start[.. + 1])
+ * of `rows` ((n, 4): h, z, x, y in pixels); row_nan[i] is non-zero where candidate i holds a NaN in any column of the
+ * caller's table.  cap_start (G + 1): where each region's merged rows start; region g must get room for its candidates
+ * plus 2 * n_chrom rows.
+ *   ia3_cellpick_merge_dev   merge_spot_list (:662-765) of every region, the merged rows kept on the device.  has_th == 0:
+ *                            intensity_th None.  Out: count / valid (G) merged rows and those of them without a NaN;
+ *                            src (cap_start[G]): per merged row its candidate, or -(1 + chromosome) for a placeholder.
+ *   ia3_cellpick_naive_dev   the selections of naive_pick_spots_for_chromosomes (:854-888): mode _NAIVE_OWN picks per
+ *                            chromosome among its own candidates (pick: the candidate or -1), _NAIVE_MERGED among the merged
+ *                            rows nearest to its coordinate (pick: the merged row of the region, sub: its index among the
+ *                            chromosome's rows).  pick / sub: (G, IA3_CELLPICK_MAX_CHROM).
+ *   ia3_cellpick_plan        the regions each cell's forward pass walks, in its order: cell k walks
+ *                            vreg[vstart[k] .. vstart[k + 1]); vgap: the id of each minus the id of the one before (0 for
+ *                            the first).  Every region named must have 1 to IA3_CELLPICK_MAX_SPOTS merged rows.
+ *   ia3_cellpick_forward_dev the forward pass (:1093-1155) of the n_active cells `cells` (ascending).  scores
+ *                            (max n_chrom, cap_start[G]): per chromosome the score of every merged row; kind:
+ *                            IA3_SCORE_KIND_DIST_LINEAR with ref_scalar (n_cells, IA3_CELLPICK_MAX_CHROM), or _DIST_CDF with
+ *                            per (cell, chromosome) the sorted reference values [ref_start[j], ref_start[j + 1]) of `sorted`
+ *                            and the ref_start[j + 1] - ref_start[j] + 1 scores at table[ref_start[j] + j ..].  Out: dy, the
+ *                            dynamic scores, and ptr, the chosen row of the region before (255 where none), laid out as
+ *                            scores; err (n_cells): 0, 1 where no tuple of distinct rows exists, 2 where no sum is a number,
+ *                            3 where a spot would walk more than IA3_CELLPICK_MAX_TUPLES index tuples (every score of a
+ *                            chromosome infinite, so all its rows are allowed): that spot is not picked.
+ *                            The planes: scores, dy and ptr hold one plane of cap_start[G] values per chromosome up to the
+ *                            largest n_chrom of the population, not IA3_CELLPICK_MAX_CHROM.  _NAIVE_MERGED picks nothing
+ *                            for a cell without coordinates.
+ * IA3_EINVAL before any launch for null pointers, offsets that do not ascend, more chromosomes than built, and regions,
+ * cells or reference ranges out of bounds. */
+#define IA3_CELLPICK_MAX_CHROM 6
+#define IA3_CELLPICK_MAX_SPOTS 64
+#define IA3_CELLPICK_MAX_TUPLES 4194304
+#define IA3_CELLPICK_NAIVE_OWN 0
+#define IA3_CELLPICK_NAIVE_MERGED 1
+int ia3_cellpick_create(const double* rows, const unsigned char* row_nan, const int* cand_start, const int* region_start,
+                        const int* n_chrom, const double* coords, const int* has_coords, const int* cap_start, int n_cells,
+                        int G, const double* distance_zxy, void** out);
+void ia3_cellpick_free(void* population);
+int ia3_cellpick_merge_dev(void* population, int has_th, double intensity_th, int hard, double dist_th, int* count, int* valid,
+                           int* src);
+int ia3_cellpick_naive_dev(void* population, int mode, int* pick, int* sub);
+int ia3_cellpick_plan(void* population, const int* vstart, const int* vreg, const long long* vgap);
+int ia3_cellpick_forward_dev(void* population, const int* cells, int n_active, const double* scores, int kind,
+                             const double* ref_scalar, const int* ref_start, const double* sorted, const double* table,
+                             double weight, double limit_hi, double nan_mask, int share, double* dy, unsigned char* ptr, int* err);
+
 /* ---- whole round-folder movies: the per-image task of classes/batch_functions.py:60-302 batch_process_image_to_spots
  * (fanned out over an mp.Pool by classes/field_of_view.py:1027-1142), as ONE pipelined call over many movies -------------
  * Per movie: raw (frames, X, Y) uint16 movie from host memory or a .dax file -> split_im_by_channels
